@@ -12,8 +12,15 @@ over xGMI): under torch.distributed.run (the driver's launch; --gpus must equal 
 the bench exits with status 2), or, started without it, the bench starts torch.distributed.run
 itself as a child process before anything touches the GPU and exits with its status.  Rank 0 prints ONE
 JSON line with the roofline of the dominant kernel (HIP events on the launch
-stream inside the timed region) and the CPU baseline (the oracle, i.e. the
-reference's op sequence restated, timed on a bounded sample on the host cores).
+stream inside the timed region).
+
+A plain run does only what that line's headline needs: set up, W warm-up steps, K timed steps, the line.
+--full adds, after the timed steps, everything else the benchmark measures or checks: the parity check
+against the fp64 CPU oracle, the CPU baseline (the oracle, i.e. the reference's op sequence restated, timed
+on a bounded sample on the host cores), the one-stream profiling pass behind the roofline of the
+generic-size workloads and, for c3, the extra workloads (C3 at 100 iterations, C3 iso, bsd, hd, the training
+step, the C5 model step); --no-cpu-baseline, --no-parity, --no-extras and --no-c5-extra drop single legs of it.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -113,14 +120,22 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: the parity "
+                         "check against the fp64 CPU oracle, the CPU baseline, the one-stream profiling pass of the "
+                         "generic-size roofline and (c3) the extra workloads; the --no-* options below switch single "
+                         "legs of it off.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32 or "
+                         "float64; a fixed seeded sample of an output larger than the size limit)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity checks")
     ap.add_argument("--no-extras", action="store_true",
-                    help="c3: skip the extra measurements after the timed region (C3 at 100 iterations, C3 iso, "
+                    help="--full, c3: skip the extra measurements after the timed region (C3 at 100 iterations, C3 iso, "
                          "the generic-size bsd / hd workloads, the training step)")
     ap.add_argument("--no-c5-extra", action="store_true",
-                    help="c3: skip the whole C5 model step after the other extras (its first step compiles MIOpen's "
-                         "kernels: minutes on a fresh box)")
+                    help="--full, c3: skip the whole C5 model step after the other extras (its first step compiles "
+                         "MIOpen's kernels: minutes on a fresh box)")
     ap.add_argument("--cpu-planes", type=int, default=6, help="CPU baseline sample: planes of 1024^2")
     ap.add_argument("--cpu-iters", type=int, default=36, help="CPU baseline sample: timed iterations")
     ap.add_argument("--batch", type=int, default=None,
@@ -131,6 +146,33 @@ def parse():
     ap.add_argument("--c5-channels-last", action="store_true", help="C5 only: NHWC activations (MIOpen NHWC convs)")
     ap.add_argument("--c5-conv-benchmark", action="store_true", help="C5 only: MIOpen find (cudnn.benchmark)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 48 * 2**20  # all files of one --dump-outputs run together (under 64 MB)
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirpath, arrays):
+    """Write the last timed step's results as dirpath/<name>.npy, float32 (float64 for a float64 tensor).
+    The files share DUMP_LIMIT_BYTES equally; a tensor above its share is written as a sample: its elements
+    at sorted flat indices drawn once from a generator seeded with DUMP_SEED (the same indices for the same
+    shape in every run and every build, so two runs compare element for element)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        flat = t.reshape(-1)
+        room = share // flat.element_size()
+        if flat.numel() > room:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, flat.numel(), (room,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+            a = flat.cpu().numpy()
+        else:
+            a = t.cpu().numpy()
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def pmc_traffic(config: str, kernel: str, launches: int, steps: int, build_hash: str):
@@ -429,7 +471,9 @@ def c5_session(dev, B, rank=0, world=1, ckpt=True, channels_last=False, conv_ben
         loss = (out.float() - y).abs().mean()
         loss.backward()
         opt.step()
+        step.out = out.detach()  # the last step's model output (--dump-outputs)
         return loss
+    step.out = None
     return step
 
 
@@ -519,6 +563,8 @@ def run_c5(args, world, rank, dev):
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     T = elapsed.item()
     K = args.steps
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": step.out, "loss": loss.detach().reshape(1)})
     if rank == 0:
         admm_ms = sum(ms)
         print(json.dumps({
@@ -534,7 +580,7 @@ def run_c5(args, world, rank, dev):
                            "launches_per_step": sum(cnt) / K},
             "peak_mem_GiB": torch.cuda.max_memory_allocated(dev) / 2**30,
             "loss": float(loss.detach()),
-            "cpu_baseline": cpu_baseline_c5() if (world == 1 and not args.no_cpu_baseline) else None}),
+            "cpu_baseline": cpu_baseline_c5() if (args.full and world == 1 and not args.no_cpu_baseline) else None}),
               flush=True)
 
 
@@ -697,6 +743,8 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     T = elapsed.item()
     progress(f"timed region done ({T:.2f} s)")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out})  # the deconvolved batch the last timed solve returned
 
     P = B * C
     npx = P * H * W
@@ -709,10 +757,13 @@ def main():
     # The generic aniso inference solve runs two plane halves on two streams (ADMM_GEN_STREAMS): the
     # event times of its launches overlap and do not add up to kernel durations.  Its roofline then
     # comes from a separate profiling pass of the same solve on one stream (after the timed region;
-    # the headline value is the timed region's).
+    # the headline value is the timed region's), which is a run of its own: --full only.
     two_stream = (generic or odd) and not iso and P >= 2 and os.environ.get("ADMM_GEN_STREAMS", "2") != "1"
     roof_steps, roof_note = K, "HIP events of every launch inside the timed region"
-    if two_stream:
+    if two_stream and not args.full:
+        roof_note += (": the timed solves run two plane halves on two streams, whose launches overlap, so the "
+                      "per-kernel times are upper bounds (--full adds a one-stream profiling pass)")
+    if two_stream and args.full:
         roof_steps = min(K, 5)
         os.environ["ADMM_GEN_STREAMS"] = "1"
         try:
@@ -748,7 +799,7 @@ def main():
 
     traffic, traffic_src = pmc_traffic(args.config, dom, dn, roof_steps, build_hash)
     parity = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         from oracle.admm_oracle import rel_l2, solve_fourier
         ref = solve_fourier(x[:1, :1].double().cpu(), 0.01, 0.02, psf.double().cpu(), iso, maxit) \
             if not iso else None
@@ -756,7 +807,7 @@ def main():
             parity = {"rel_l2": rel_l2(out[:1, :1].cpu(), ref),
                       "vs": "fp64 CPU oracle (pinned to the reference), plane (0,0) of the last step"}
     extras = {}
-    if rank == 0 and world == 1 and args.config == "c3" and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and args.config == "c3" and not args.no_extras:
         extras = c3_extras(x, psf, lam, rho, args.no_parity)
         del out, x  # free the C3 batch before the other workloads
         torch.cuda.empty_cache()
@@ -767,7 +818,7 @@ def main():
     result = None
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(cfg, args.cpu_planes, args.cpu_iters)
         value = world * maxit * K / T
         it_bytes = (PASS_A_BYTES + (gen_col if generic else PASS_B_BYTES) + (ISO_NORM_BYTES if iso else 0)) * npx

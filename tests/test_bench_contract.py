@@ -115,6 +115,36 @@ def test_rocfft_rank_cache(monkeypatch):
     assert os.environ["ROCFFT_RTC_CACHE_PATH"] == "/somewhere/mine.db"
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full is off by default (a plain run measures the headline only) and --dump-outputs takes a directory."""
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """A result within its share of the limit is written whole; a larger one as the elements at the same sorted
+    seeded flat indices in every call; float32, or float64 for a float64 tensor."""
+    import numpy as np
+    import torch
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    big = torch.arange(5000, dtype=torch.bfloat16).reshape(50, 100)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 1000 * 4)  # two files: 1000 float32 values each
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())
+    assert b.dtype == np.float32 and b.shape == (1000,)
+    idx = torch.randint(0, 5000, (1000,), generator=torch.Generator().manual_seed(bench.DUMP_SEED)).sort().values
+    assert len(idx.unique()) > 800 and np.array_equal(b, big.float().reshape(-1)[idx].numpy())
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 2 * 1000 * 4 + 2 * 128  # + .npy headers
+
+
 def test_mm_col_flops_plan():
     # BSD columns 321 = 3 * 107: h = 53 -> 64-row tiles, 56-deep k; forward + inverse, cos + sin, re + im
     import bench

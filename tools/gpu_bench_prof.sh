@@ -6,6 +6,8 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 TAG=${TAG:-run}
+# the recorded line is the full one (parity, CPU baseline, extra workloads); BENCH_ARGS given by the caller replace it
+BENCH_ARGS=${BENCH_ARGS:---full}
 mkdir -p gpurun_out/$TAG
 if [ -n "$MIMIC" ]; then
   env $MIMIC=1 timeout -k 10 300 tools/membench/stream_mimic > gpurun_out/$TAG/mimic.txt 2>&1 || { echo mimic_fail; exit 1; }
