@@ -346,9 +346,26 @@ template <int N> struct RowOps {
     template <bool ISO, bool FIRST, bool HIST, bool PL> static void pa(const PassAArgs& a, unsigned nb, hipStream_t s) {
         hipLaunchKernelGGL((k_pass_a<N, ISO, FIRST, HIST, PL>), dim3(nb), dim3(G::NT), G::lds_bytes(), s, a);
     }
-    static int pass_a(const PassAArgs& a, bool iso, bool first, bool hist, hipStream_t s, bool pl = false) {
+    // the cooperative variant (admm_kernels.hpp k_pass_a COOP): aniso inference at 1,024-pixel rows
+    // (sub-groups of one wave; the iso variant of it spills at 3 waves per SIMD and is not built)
+    static constexpr bool kCoop = N == 512;
+    template <bool FIRST, bool PL> static void pa_coop(const PassAArgs& a, unsigned nb, hipStream_t s) {
+        if constexpr (kCoop)
+            hipLaunchKernelGGL((k_pass_a<N, false, FIRST, false, PL, true>), dim3(nb), dim3(G::NT), passa_coop_lds<N>(), s, a);
+    }
+    // coop: launch the cooperative variant where it can run -- whole blocks of SG strips inside one
+    // plane (its exchange barriers need every wave of a block), strips of two rows or more
+    static int pass_a(const PassAArgs& a, bool iso, bool first, bool hist, hipStream_t s, bool pl = false,
+                      bool coop = false) {
         const unsigned nb = blocks(a.nstrips);
         const int sel = (iso ? 4 : 0) | (first ? 2 : 0) | (hist ? 1 : 0);
+        if (kCoop && coop && !iso && !hist && !a.rev && a.R >= 2 && a.nstrips % G::SG == 0 &&
+            (a.H / a.R) % G::SG == 0) {
+            static_assert(!kCoop || passa_coop_lds<N>() <= 53 * 1024, "three blocks of the row pass per CU");
+            if (first) pl ? pa_coop<true, true>(a, nb, s) : pa_coop<true, false>(a, nb, s);
+            else pl ? pa_coop<false, true>(a, nb, s) : pa_coop<false, false>(a, nb, s);
+            return launch_check("k_pass_a");
+        }
         if (pl && !hist) {  // inference: lane-paired images
             switch (sel) {
                 case 0: pa<false, false, false, true>(a, nb, s); break;
@@ -1702,6 +1719,7 @@ int run_forward_mixed(const admm_tv_desc& d, const Layout& Lo, const float* xin,
             uyi = u[2 * uin + 1];
             uxo = u[2 * (1 - uin)];
             uyo = u[2 * (1 - uin) + 1];
+            if (it == d.maxit - 1) uxo = uyo = nullptr;  // the solve's last row pass writes no u (as run_forward)
         }
         const float* nsq = nullptr;
         if (d.iso) {
@@ -1833,6 +1851,8 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
     const float* cb = bimg + io;
     float* cout = out + io;
     const int R = strip_rows(H, N, crows, !d.iso && !hist);
+    // A/B knob of the cooperative row pass (RowOps::pass_a): 0 = the plain kernel
+    const bool coop = env_int("ADMM_PASSA_COOP", 1) != 0;
 
     int cur = 0, uin = 0;  // spec[cur] holds the current r spectra; u[2*uin], u[2*uin+1] = u_x, u_y in
     for (int it = 1; it <= d.maxit; ++it) {
@@ -1862,6 +1882,9 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
             uyi = u[2 * uin + 1] + io;
             uxo = u[2 * (1 - uin)] + io;
             uyo = u[2 * (1 - uin) + 1] + io;
+            // the last row pass of the solve: only its r spectra are used (the last column pass and
+            // the output transform follow), so it writes no u (k_pass_a: a null output)
+            if (it == d.maxit - 1) uxo = uyo = nullptr;
         }
         const float* nsq = nullptr;
         if (d.iso) {
@@ -1888,7 +1911,9 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
             cf* tout = (keep_t && it < d.maxit) ? ht(it + 1) : cspec[1 - cur];
             PassAArgs pa{cspec[cur], tout, cb, uxi, uyi, uxo, uyo, nsq, nprev, lam, rho, twW, H, R, crows / R, ppm,
                          env_int("ADMM_PASSA_REV", 0)};
-            int e = with_row(N, [&](auto ops) { return decltype(ops)::pass_a(pa, d.iso != 0, first, train, st, pl); });
+            int e = with_row(N, [&](auto ops) {
+                return decltype(ops)::pass_a(pa, d.iso != 0, first, train, st, pl, coop);
+            });
             if (e) return e;
         }
         cur = 1 - cur;

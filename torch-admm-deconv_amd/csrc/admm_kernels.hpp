@@ -653,17 +653,31 @@ __device__ __forceinline__ cf prev_u(const cf* __restrict__ src, const cf* __res
     }
 }
 
-template <int N, bool ISO, bool FIRST, bool HIST, bool PL>
+// COOP (the cooperative variant, inference, full-wave sub-groups): the SG strips of a block are
+// consecutive strips of one plane; even sub-groups walk their strip downwards, odd ones upwards, so
+// the rows on both sides of every boundary inside the block are in registers at the same moment and
+// pass through LDS (x one way, w_y back) instead of being transformed and read by both strips.  Only
+// the block's two outer halos are still recomputed: 2 halo c2r and 1 halo u_y row per block instead
+// of 2 and 1 per strip.  Every pixel sees the same operands in the same order in both directions, so
+// the results are those of the plain kernel bit for bit.  The host launches it only with
+// nstrips % SG == 0, (H / R) % SG == 0 and R >= 2 (RowOps::pass_a): every wave of a block then
+// reaches each of the four exchange barriers, all of which sit on the block-uniform path.
+template <int N> constexpr size_t passa_coop_lds() {
+    return RowKernelGeom<N>::lds_bytes() + sizeof(cf) * (RowKernelGeom<N>::SG - 1) * N;
+}
+template <int N, bool ISO, bool FIRST, bool HIST, bool PL, bool COOP = false>
 __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
     static_assert(!(PL && HIST), "the training history keeps the pixel-order layout");
     using G = RowKernelGeom<N>;
-    constexpr int E = G::E, L = G::L, W = G::W;
+    constexpr int E = G::E, L = G::L, W = G::W, SG = G::SG;
+    static_assert(!COOP || (L == 64 && SG % 2 == 0 && !HIST && !ISO), "cooperative strips: whole waves in pairs, aniso inference");
     constexpr bool kSpecNT = (ADMM_NT & 2) != 0 || ((ADMM_NT & 32) != 0 && N >= 512);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     cf* tw = reinterpret_cast<cf*>(smem);
     load_tw(tw, a.twW, W);
     __syncthreads();
-    const int sgl = threadIdx.x / L, t = threadIdx.x % L;
+    // (COOP: a sub-group is a wave, and its role below is decided on scalar registers)
+    const int sgl = COOP ? __builtin_amdgcn_readfirstlane(threadIdx.x / L) : threadIdx.x / L, t = threadIdx.x % L;
     // XCD remap of the strips (-DADMM_PASSA_REMAP=0/1 for A/B runs; default: W <= 512): C2
     // pass A +2 %, C3 -7 % (interleaved A/B, tools/ab_variants.sh)
 #ifndef ADMM_PASSA_REMAP
@@ -672,8 +686,10 @@ __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
     constexpr bool kRemap = ADMM_PASSA_REMAP < 0 ? N <= 256 : ADMM_PASSA_REMAP != 0;
     const unsigned blk = kRemap ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
     long long strip = (long long)blk * G::SG + sgl;
-    if (strip >= a.nstrips) return;
-    if (a.rev) strip = a.nstrips - 1 - strip;
+    if constexpr (!COOP) {  // (COOP: whole blocks only, and no return ahead of the exchange barriers)
+        if (strip >= a.nstrips) return;
+        if (a.rev) strip = a.nstrips - 1 - strip;
+    }
     const int H = a.H, R = a.R;
     const int spp = H / R;
     const long long p = strip / spp;
@@ -689,30 +705,28 @@ __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
     const cf* bimg = reinterpret_cast<const cf*>(a.b + (size_t)(p - (long long)mod * a.ppm) * H * W);
     const cf* uxi = reinterpret_cast<const cf*>(a.uxi + poff);
     const cf* uyi = reinterpret_cast<const cf*>(a.uyi + poff);
-    cf* uxo = reinterpret_cast<cf*>(a.uxo + poff);
-    cf* uyo = reinterpret_cast<cf*>(a.uyo + poff);
+    // no u output: the last row pass of an inference solve, whose u nobody reads (only its r spectra
+    // are); a kernel argument, so the test is wave-uniform
+    const bool ust = HIST || a.uxo != nullptr;
+    cf* uxo = ust ? reinterpret_cast<cf*>(a.uxo + poff) : nullptr;
+    cf* uyo = ust ? reinterpret_cast<cf*>(a.uyo + poff) : nullptr;
     const size_t moff = (size_t)mod * 2 * H * W;  // this module's norm maps
     const cf* nsx = reinterpret_cast<const cf*>(a.nsq + moff);
     const cf* nsy = reinterpret_cast<const cf*>(a.nsq + moff + (size_t)H * W);
     const cf* npx = reinterpret_cast<const cf*>(a.nsq_prev + moff);
     const cf* npy = reinterpret_cast<const cf*>(a.nsq_prev + moff + (size_t)H * W);
 
-    cf xprev[E], xcur[E], wxp[E], wyp[E];
-    {
-        const int g = (i0 - 1 + H) & (H - 1);
+    // The parts of a row step.  A strip walked downwards runs them for rows i0 .. i0 + R with the row
+    // above in hand; walked upwards (COOP) it runs the same parts with the row below in hand.
+    // row g's x (spectrum row -> c2r)
+    auto xrow = [&](int g, cf (&x)[E]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < E; ++j) xprev[j] = ld_pol<kSpecNT>(&sp[(size_t)g * N + t + L * j]);
-        RowXf<N>::c2r(xprev, buf, tw, t);
-    }
-    for (int rr = 0; rr <= R; ++rr) {
-        const int g = (i0 + rr) & (H - 1);
+        for (int j = 0; j < E; ++j) x[j] = ld_pol<kSpecNT>(&sp[(size_t)g * N + t + L * j]);
+        RowXf<N>::c2r(x, buf, tw, t);
+    };
+    // ---- y direction: a_y = x[g] - x[g-1] + u_y; z_y, u_y (stored if `store`), w_y of row g
+    auto ydir = [&](int g, const cf (&xg)[E], const cf (&xup)[E], bool store, cf (&wyc)[E]) __attribute__((always_inline)) {
         const size_t ro = (size_t)g * N;  // row offset in cf units (spectrum and pixel pairs alike)
-#pragma unroll
-        for (int j = 0; j < E; ++j) xcur[j] = ld_pol<kSpecNT>(&sp[ro + t + L * j]);
-        RowXf<N>::c2r(xcur, buf, tw, t);
-
-        // ---- y direction: a_y = x[g] - x[g-1] + u_y; z_y, u_y, w_y of row g
-        cf wyc[E];
         {
             cf uy[E], fy[E];
             if constexpr (PL) {
@@ -732,15 +746,15 @@ __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
             }
 #pragma unroll
             for (int j = 0; j < E; ++j) {
-                const float a0 = (xcur[j].x - xprev[j].x) + uy[j].x;
-                const float a1 = (xcur[j].y - xprev[j].y) + uy[j].y;
+                const float a0 = (xg[j].x - xup[j].x) + uy[j].x;
+                const float a1 = (xg[j].y - xup[j].y) + uy[j].y;
                 const float z0 = shrink_z<ISO>(a0, tau, ISO ? fy[j].x : 0.f);
                 const float z1 = shrink_z<ISO>(a1, tau, ISO ? fy[j].y : 0.f);
                 const float n0 = a0 - z0, n1 = a1 - z1;  // u_y(new)
                 uy[j] = HIST ? mkc(a0, a1) : mkc(n0, n1);
                 wyc[j] = mkc(z0 - n0, z1 - n1);
             }
-            if (rr < R) {
+            if (store && ust) {
                 if constexpr (PL) {
                     st_row<E, L, true, (ADMM_NT & 1) != 0>(uyo + ro, t, uy);
                 } else {
@@ -749,10 +763,10 @@ __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
                 }
             }
         }
-
-        // ---- finalize row g-1: v = Dx^T w_x + Dy^T w_y, r = b + rho v, row FFT
-        if (rr >= 1) {
-            const int gm = (g - 1 + H) & (H - 1);
+    };
+    // ---- finalize row gm: v = Dx^T w_x + Dy^T w_y (wyp, wyc: w_y of rows gm, gm + 1), r = b + rho v, row FFT
+    auto finish = [&](int gm, const cf (&wxp)[E], const cf (&wyp)[E], const cf (&wyc)[E]) __attribute__((always_inline)) {
+        {
             const size_t rm = (size_t)gm * N;
             cf r[E], sh[E], bv[E];
             if constexpr (PL) ld_row<E, L, true, (ADMM_NT & 16) != 0>(bimg + rm, t, bv);
@@ -770,9 +784,11 @@ __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
 #pragma unroll
             for (int j = 0; j < E; ++j) sta(&so[rm + t + L * j], r[j]);
         }
-
-        // ---- x direction: a_x = x[g][j] - x[g][j-1] + u_x; z_x, u_x, w_x of row g
-        if (rr < R) {
+    };
+    // ---- x direction: a_x = x[g][j] - x[g][j-1] + u_x; z_x, u_x, w_x of row g
+    auto xdir = [&](int g, const cf (&xcur)[E], cf (&wxp)[E]) __attribute__((always_inline)) {
+        const size_t ro = (size_t)g * N;
+        {
             cf ux[E], fx[E], sh[E];
             if constexpr (PL) {
                 if constexpr (FIRST) {
@@ -802,18 +818,107 @@ __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
                 ux[j] = HIST ? mkc(a0, a1) : mkc(n0, n1);
                 wxp[j] = mkc(z0 - n0, z1 - n1);
             }
-            if constexpr (PL) {
-                st_row<E, L, true, (ADMM_NT & 1) != 0>(uxo + ro, t, ux);
-            } else {
+            if (ust) {
+                if constexpr (PL) {
+                    st_row<E, L, true, (ADMM_NT & 1) != 0>(uxo + ro, t, ux);
+                } else {
 #pragma unroll
-                for (int j = 0; j < E; ++j) sta(&uxo[ro + t + L * j], ux[j]);
+                    for (int j = 0; j < E; ++j) sta(&uxo[ro + t + L * j], ux[j]);
+                }
             }
         }
+    };
+
+    // state carried from row to row: x, w_y of the row walked last (xprev, wyp), w_x of the row to finalize
+    cf xprev[E], xcur[E], wxp[E], wyp[E], wyc[E];
+    // One row step at row g.  Downwards it completes a_y of row g (x[g] - x[g-1]) and finalizes row
+    // g - 1; upwards (COOP) it completes a_y of row g + 1 (x[g+1] - x[g]) and finalizes row g + 1;
+    // either way then w_x of row g.  `up` is a constant of the plain walk and uniform over a wave in
+    // COOP, where it only picks which of the two rows in hand is the upper one (selects on a scalar
+    // condition: two instances of the step, one per direction, did not fit the 168 registers).
+    auto pick = [](bool c, cf p, cf q) __attribute__((always_inline)) { return mkc(c ? p.x : q.x, c ? p.y : q.y); };
+    // a_y, u_y, w_y (-> wyc) of row gy, the lower of the two rows in hand
+    auto ystep = [&](bool up, int gy, bool store) __attribute__((always_inline)) {
+        cf xg[E], xup[E];
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            xg[j] = pick(up, xprev[j], xcur[j]);
+            xup[j] = pick(up, xcur[j], xprev[j]);
+        }
+        ydir(gy, xg, xup, store, wyc);
+    };
+    // finalize row gf, whose w_y is wyp (downwards) or wyc (upwards)
+    auto fstep = [&](bool up, int gf) __attribute__((always_inline)) {
+        cf wa[E], wb[E];
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            wa[j] = pick(up, wyc[j], wyp[j]);
+            wb[j] = pick(up, wyp[j], wyc[j]);
+        }
+        finish(gf, wxp, wa, wb);
+    };
+    auto shift = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             wyp[j] = wyc[j];
             xprev[j] = xcur[j];
         }
+    };
+    auto step = [&](bool up, int g, bool ystore, bool fin, bool xd) __attribute__((always_inline)) {
+        xrow(g, xcur);
+        const int gn = up ? (g + 1) & (H - 1) : g;
+        ystep(up, gn, ystore);
+        if (fin) fstep(up, up ? gn : (g - 1 + H) & (H - 1));
+        if (xd) xdir(g, xcur, wxp);
+        shift();
+    };
+    if constexpr (!COOP) {
+        xrow((i0 - 1 + H) & (H - 1), xprev);
+        for (int rr = 0; rr <= R; ++rr) step(false, (i0 + rr) & (H - 1), rr < R, rr >= 1, rr < R);
+    } else {
+        // one mailbox of a row (register layout t + L j) per boundary between two sub-groups: boundary s
+        // lies between sub-groups s and s + 1.  Odd boundaries are met at the start of the walks (an
+        // up-walker above a down-walker), even ones at their end.  A mailbox carries x downwards, then
+        // w_y back up, with a barrier between accesses of different waves.
+        cf* mbox = tw + W + SG * RowBuf::slots(N);
+        const bool up = (sgl & 1) != 0, top = sgl == 0, bot = sgl == SG - 1;  // wave-uniform
+        cf* mbs = mbox + (size_t)min(max(up ? sgl : sgl - 1, 0), SG - 2) * N;  // (unused by top / bot)
+        cf* mbe = mbox + (size_t)(up ? sgl - 1 : sgl) * N;
+        auto put = [&](cf* mb, const cf (&v)[E]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) mb[t + L * j] = v[j];
+        };
+        auto get = [&](const cf* mb, cf (&v)[E]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) v[j] = mb[t + L * j];
+        };
+        const int gs = up ? i0 + R - 1 : i0;  // the strip's first row (strips inside a block never wrap)
+        // the block's outer halos: the row above it, the row below it
+        if (top || bot) xrow((top ? i0 - 1 + H : i0 + R) & (H - 1), xprev);
+        xrow(gs, xcur);
+        if (up && !bot) put(mbs, xcur);
+        lds_barrier();  // 1: x of the row above each odd boundary
+        if (!up && !top) get(mbs, xprev);
+        // a down-walker's first row; the row below the block (its w_y only)
+        if (!up || bot) ystep(up, up ? (i0 + R) & (H - 1) : gs, !up);
+        if (!up && !top) put(mbs, wyc);
+        lds_barrier();  // 2: w_y of the row below each odd boundary
+        if (up && !bot) get(mbs, wyc);
+        xdir(gs, xcur, wxp);
+        shift();
+        for (int rr = 1; rr < R; ++rr) step(up, up ? i0 + R - 1 - rr : i0 + rr, true, true, true);
+        // the strips meet at the even boundaries: a down-walker holds x, w_x, w_y of its last row
+        // i0 + R - 1, the up-walker below it x, w_x of its last row i0 and w_y of row i0 + 1
+        if (!up) put(mbe, xprev);
+        lds_barrier();  // 3: x of the row above each even boundary
+        if (up) {
+            get(mbe, xcur);
+            ystep(true, i0, true);
+            put(mbe, wyc);
+        }
+        lds_barrier();  // 4: w_y of the row below each even boundary
+        if (!up) get(mbe, wyc);
+        fstep(up, up ? i0 : i0 + R - 1);
     }
 }
 

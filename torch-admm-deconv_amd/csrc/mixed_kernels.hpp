@@ -747,8 +747,10 @@ __global__ void __launch_bounds__(256, PASSA_M_MINW((MPlan<N, HIST>::Ep))) k_pas
     const cf* bimg = reinterpret_cast<const cf*>(a.b + poff);
     const cf* uxi = reinterpret_cast<const cf*>(a.uxi + poff);
     const cf* uyi = reinterpret_cast<const cf*>(a.uyi + poff);
-    cf* uxo = reinterpret_cast<cf*>(a.uxo + poff);
-    cf* uyo = reinterpret_cast<cf*>(a.uyo + poff);
+    // no u output: the last row pass of an inference solve (admm_kernels.hpp k_pass_a)
+    const bool ust = HIST || a.uxo != nullptr;
+    cf* uxo = ust ? reinterpret_cast<cf*>(a.uxo + poff) : nullptr;
+    cf* uyo = ust ? reinterpret_cast<cf*>(a.uyo + poff) : nullptr;
     const cf* nsx = reinterpret_cast<const cf*>(a.nsq);
     const cf* nsy = reinterpret_cast<const cf*>(a.nsq + (size_t)H * W);
     const cf* npx = reinterpret_cast<const cf*>(a.nsq_prev);
@@ -792,7 +794,7 @@ __global__ void __launch_bounds__(256, PASSA_M_MINW((MPlan<N, HIST>::Ep))) k_pas
                 uy[j] = HIST ? mkc(a0, a1) : mkc(n0, n1);
                 wyc[j] = mkc(z0 - n0, z1 - n1);
             }
-            if (rr < R && pst) {
+            if (rr < R && pst && ust) {
 #pragma unroll
                 for (int j = 0; j < Ep; ++j) sta(&uyo[ro + t + Lp * j], uy[j]);
             }
@@ -845,7 +847,7 @@ __global__ void __launch_bounds__(256, PASSA_M_MINW((MPlan<N, HIST>::Ep))) k_pas
                 ux[j] = HIST ? mkc(a0, a1) : mkc(n0, n1);
                 wxp[j] = mkc(z0 - n0, z1 - n1);
             }
-            if (pst) {
+            if (pst && ust) {
 #pragma unroll
                 for (int j = 0; j < Ep; ++j) sta(&uxo[ro + t + Lp * j], ux[j]);
             }
