@@ -11,7 +11,8 @@ results do not depend on the strip height.
 
 The iso variant of the cooperative kernel is not built (it does not fit 3 waves per SIMD without
 spilling) and the odd-length row pass keeps its u stores (its deferred stores are a different loop), so
-neither has a case here."""
+neither has a case here.  The training side -- the history row pass that RowOps::pass_a keeps on the plain
+kernel (!hist), beside the cooperative one at the same shape -- is in tests/test_gpu_train_shapes.py."""
 import pytest
 import torch
 
