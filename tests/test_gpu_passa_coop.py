@@ -98,7 +98,7 @@ def test_coop_vs_fp64_oracle(cuda_dev, monkeypatch, it):
 
 @pytest.mark.parametrize("it", [2, 5])
 def test_mixed_radix_last_pass_without_u(cuda_dev, monkeypatch, it):
-    """240 x 480 runs the mixed-radix row pass (run_forward_mixed), whose last launch writes no u either:
+    """240 x 480 runs the mixed-radix row pass (fused_forward on MixedOps), whose last launch writes no u either:
     against the fp64 oracle, and equal to the A/B build's solve."""
     from admmtor import _native
     from oracle.admm_oracle import solve_fourier

@@ -162,7 +162,7 @@ struct Layout {
     // generic path: the matrix-core plans, decided once per call (their environment knobs are read
     // here only, so the regions sized below and the kernels launched later always agree)
     MMPlan mm, mmr;
-    // mixed-radix fused iteration (mixed_hw; run_forward_mixed): the Wiener factor for its column pass.
+    // mixed-radix fused iteration (mixed_hw; fused_forward on MixedOps): the Wiener factor for its column pass.
     // mixed_train: training forward / backward on it too (not with a PSF gradient, whose column-spectrum
     // history is the generic path's)
     bool mixed, mixed_train;
@@ -188,6 +188,8 @@ admm_tv_desc transposed(const admm_tv_desc& d) {
     admm_tv_desc t = d;
     t.H = d.W;
     t.W = d.H;
+    t.kh = d.kw;
+    t.kw = d.kh;
     return t;
 }
 
@@ -302,6 +304,18 @@ template <class K> int set_lds(K kern, size_t bytes) {
 int launch_check(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ADMM_TV_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+    return 0;
+}
+
+// a launcher's hipError_t (mixed_capi.hpp) as the library's error code, with the kernel's name
+int hip_code(hipError_t e, const char* what) {
+    return e == hipSuccess ? 0 : fail(ADMM_TV_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// the caller's workspace: given, large enough for the call's layout, 256-byte aligned
+int check_workspace(const void* ws, size_t have, size_t need) {
+    if (!ws || have < need || (reinterpret_cast<uintptr_t>(ws) % kAlign) != 0)
+        return fail(ADMM_TV_EWORKSPACE, "workspace too small or not 256-byte aligned");
     return 0;
 }
 
@@ -445,6 +459,22 @@ template <class F> int with_row(int N, F&& f) {
 }
 
 // ------------------------------------------------------------------ column-side ops (templated on H, C)
+// f(integral_constant H) for the power-of-two column lengths
+template <class F> int with_col(int H, F&& f) {
+    switch (H) {
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 512: return f(std::integral_constant<int, 512>{});
+        case 1024: return f(std::integral_constant<int, 1024>{});
+        case 2048: return f(std::integral_constant<int, 2048>{});
+        case 4096: return f(std::integral_constant<int, 4096>{});
+        default: return fail(ADMM_TV_EUNSUPPORTED, "unsupported H");
+    }
+}
+
 // column-pass tile order (k_pass_b pb_tile): planes per group, 1 = plane-major.  Two planes at
 // H >= 1024 (C3 pass B 0.376 -> 0.362 ms, C3 iso 0.381 -> 0.369; 4 and 8 planes slower: DRAM
 // locality), plane-major below (C2: neutral).  A/B knob ADMM_PASSB_GROUP.
@@ -527,18 +557,7 @@ template <int H> int pass_b_h(const cf* spec, cf* out, const float* fcT, const c
 int pass_b_oop(int H, const cf* spec, cf* out, const float* fcT, const cf* mT, const cf* twH, int N, int P, int mode,
                hipStream_t s, int ppm = 0) {
     if (ppm <= 0) ppm = P;
-    switch (H) {
-        case 16: return pass_b_h<16>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 32: return pass_b_h<32>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 64: return pass_b_h<64>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 128: return pass_b_h<128>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 256: return pass_b_h<256>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 512: return pass_b_h<512>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 1024: return pass_b_h<1024>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 2048: return pass_b_h<2048>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        case 4096: return pass_b_h<4096>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        default: return fail(ADMM_TV_EUNSUPPORTED, "unsupported H");
-    }
+    return with_col(H, [&](auto h) { return pass_b_h<decltype(h)::value>(spec, out, fcT, mT, twH, N, P, mode, ppm, s); });
 }
 
 int pass_b(int H, cf* spec, const float* fcT, const cf* mT, const cf* twH, int N, int P, int mode, hipStream_t s,
@@ -568,18 +587,7 @@ template <int H> int xspec_h(const cf* U, const cf* V, cf* part, const cf* twH, 
     else return xspec_hc<H, 4>(U, V, part, twH, N, P, ppg, s);
 }
 int xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N, int P, int ppg, hipStream_t s) {
-    switch (H) {
-        case 16: return xspec_h<16>(U, V, part, twH, N, P, ppg, s);
-        case 32: return xspec_h<32>(U, V, part, twH, N, P, ppg, s);
-        case 64: return xspec_h<64>(U, V, part, twH, N, P, ppg, s);
-        case 128: return xspec_h<128>(U, V, part, twH, N, P, ppg, s);
-        case 256: return xspec_h<256>(U, V, part, twH, N, P, ppg, s);
-        case 512: return xspec_h<512>(U, V, part, twH, N, P, ppg, s);
-        case 1024: return xspec_h<1024>(U, V, part, twH, N, P, ppg, s);
-        case 2048: return xspec_h<2048>(U, V, part, twH, N, P, ppg, s);
-        case 4096: return xspec_h<4096>(U, V, part, twH, N, P, ppg, s);
-        default: return fail(ADMM_TV_EUNSUPPORTED, "unsupported H");
-    }
+    return with_col(H, [&](auto h) { return xspec_h<decltype(h)::value>(U, V, part, twH, N, P, ppg, s); });
 }
 
 // grouped modules train only on the fused power-of-two path (a smooth size solves them one after
@@ -651,9 +659,10 @@ int setup(const admm_tv_desc& d, const Layout& Lo, void* ws, const T* kern, cons
                 if (int e = launch_check("k_fc_pack")) return e;
             }
             if constexpr (std::is_same<T, float>::value) if (Lo.mixed) {
-                hipError_t e = admm_mixed::fc_mixed(at<float>(ws, Lo.fcT) + (size_t)g * n,
-                                                    at<float>(ws, Lo.fcM) + (size_t)g * (2 * N + 1) * H, H, N, s);
-                if (e != hipSuccess) return fail(ADMM_TV_EHIP, std::string("k_fc_mixed: ") + hipGetErrorString(e));
+                if (int e = hip_code(admm_mixed::fc_mixed(at<float>(ws, Lo.fcT) + (size_t)g * n,
+                                                          at<float>(ws, Lo.fcM) + (size_t)g * (2 * N + 1) * H, H, N, s),
+                                     "k_fc_mixed"))
+                    return e;
             }
             if constexpr (std::is_same<T, float>::value) if (Lo.gen && Lo.mm.ok && ngroups_of(d) == 1) {
                 float* fc = at<float>(ws, Lo.fcT);  // the generic path has one module (grouped: the mixed path)
@@ -663,8 +672,7 @@ int setup(const admm_tv_desc& d, const Layout& Lo, void* ws, const T* kern, cons
             }
         }
         if constexpr (std::is_same<T, float>::value) if (Lo.mixed && k > 0) {
-            hipError_t e = admm_mixed::mt_mixed(at<cf>(ws, Lo.mT), at<cf>(ws, Lo.mM), H, N, s);
-            if (e != hipSuccess) return fail(ADMM_TV_EHIP, std::string("k_mt_mixed: ") + hipGetErrorString(e));
+            if (int e = hip_code(admm_mixed::mt_mixed(at<cf>(ws, Lo.mT), at<cf>(ws, Lo.mM), H, N, s), "k_mt_mixed")) return e;
         }
     }
     return 0;
@@ -716,6 +724,10 @@ struct DeviceGuard {
     }
     ~DeviceGuard() {
         if (prev >= 0 && dev != prev) (void)hipSetDevice(prev);
+    }
+    // the entry points' check: 0, or the error of finding / selecting the stream's device
+    int check() const {
+        return err == hipSuccess ? 0 : fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(err));
     }
 };
 
@@ -1417,6 +1429,18 @@ Hist make_hist(const admm_tv_desc& d) {
     h.total = h.t_off + (h.keep_t ? (size_t)d.maxit * h.t_slot : 0);
     return h;
 }
+// a call's history buffer as typed slots (k >= 1; a backward only reads them)
+template <class T> struct HistView {
+    Hist h;
+    char* base;
+    HistView(const admm_tv_desc& d, const void* hist) : h(make_hist(d)), base(static_cast<char*>(const_cast<void*>(hist))) {}
+    T* a(int k, int comp) const {  // a_k image, comp 0 = x, 1 = y
+        return reinterpret_cast<T*>(base + (size_t)(2 * (k - 1) + comp) * h.a_slot);
+    }
+    T* n(int k) const { return reinterpret_cast<T*>(base + h.n_off + (size_t)(k - 1) * h.n_slot); }  // N_k
+    // r_k's kept spectrum (PSF gradient: h.keep_t)
+    cx_t<T>* r(int k) const { return reinterpret_cast<cx_t<T>*>(base + h.t_off + (size_t)(k - 1) * h.t_slot); }
+};
 
 
 // generic-size forward (same contract as run_forward; generic_kernels.hpp)
@@ -1436,17 +1460,8 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
     T* rimg = at<T>(ws, Lo.rimg);
     T* u[4] = {at<T>(ws, Lo.u[0]), at<T>(ws, Lo.u[1]), at<T>(ws, Lo.u[2]), at<T>(ws, Lo.u[3])};
     const bool train = hist != nullptr;
-    const Hist Hs = make_hist(d);
-    auto ha = [&](int k, int comp) -> T* {
-        return reinterpret_cast<T*>(static_cast<char*>(hist) + (size_t)(2 * (k - 1) + comp) * Hs.a_slot);
-    };
-    auto hn = [&](int k) -> T* {
-        return reinterpret_cast<T*>(static_cast<char*>(hist) + Hs.n_off + (size_t)(k - 1) * Hs.n_slot);
-    };
-    const bool keep_t = train && Hs.keep_t;  // PSF gradient: keep every r_k's 2-D spectrum
-    auto ht = [&](int k) -> C* {
-        return reinterpret_cast<C*>(static_cast<char*>(hist) + Hs.t_off + (size_t)(k - 1) * Hs.t_slot);
-    };
+    const HistView<T> hv(d, hist);
+    const bool keep_t = train && hv.h.keep_t;  // PSF gradient: keep every r_k's 2-D spectrum
     const T* bimg = xin;
     if (d.kh > 0) {  // b = H_t(xin) once
         ProfScope ps(3, s);
@@ -1503,7 +1518,7 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         const bool last = it == d.maxit;
         {
             ProfScope ps(1, st);
-            if (int e = gcol<T>(cspec, keep_t ? ht(it) : nullptr, fcT, mT, twH, H, W, np, 0, st, gs, Lo.mm, ld)) return e;
+            if (int e = gcol<T>(cspec, keep_t ? hv.r(it) : nullptr, fcT, mT, twH, H, W, np, 0, st, gs, Lo.mm, ld)) return e;
             if (int e = grow_inv<T>(cspec, last ? cout : cx, twW, W, crows, st, gs, Lo.mmr, ld)) return e;
         }
         if (last && !train) break;
@@ -1512,11 +1527,11 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         const T *uxi, *uyi, *nprev = nullptr;
         T *uxo, *uyo;
         if (train) {
-            uxi = first ? nullptr : ha(it - 1, 0);
-            uyi = first ? nullptr : ha(it - 1, 1);
-            uxo = ha(it, 0);
-            uyo = ha(it, 1);
-            if (d.iso && !first) nprev = hn(it - 1);
+            uxi = first ? nullptr : hv.a(it - 1, 0);
+            uyi = first ? nullptr : hv.a(it - 1, 1);
+            uxo = hv.a(it, 0);
+            uyo = hv.a(it, 1);
+            if (d.iso && !first) nprev = hv.n(it - 1);
         } else {
             uxi = u[2 * uin] + io;
             uyi = u[2 * uin + 1] + io;
@@ -1526,7 +1541,7 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         const T* nsq = nullptr;
         if (d.iso) {
             ProfScope ps(2, st);
-            T* nout = train ? hn(it) : at<T>(ws, Lo.nsq);
+            T* nout = train ? hv.n(it) : at<T>(ws, Lo.nsq);
             const long long hw = (long long)H * W;
             const dim3 grid((unsigned)((hw + 255) / 256)), blk(256);
             if (first)
@@ -1632,130 +1647,237 @@ int strip_rows_mixed(int H, long long rows, int N, long long slots = 0) {
     return best;
 }
 
-// The inference solve of a smooth size (mixed_hw) on the fused two-pass iteration (mixed_kernels.hpp):
-// the same sequence as run_forward's fused loop -- b = H_t(xin) once (here through the generic
-// transforms, mode 1: once per solve), r_1 = rowFFT(b), then per iteration pass B (column FFT, Wiener
-// factor, column IFFT), [iso: the norm pass, its reduce and the cross-rank hook], pass A -- inside
-// the generic layout's regions (spec[0] / spec[1] hold the packed row spectra ping-pong, u[0..3] the
-// u images; the generic b region or xin is b, in pixel order).
-// hist: the training forward (Layout::mixed_train) -- a_k and N_k into the history as run_forward's
-// fused loop writes them (make_hist), and the last iteration's pass A also runs.
-int run_forward_mixed(const admm_tv_desc& d, const Layout& Lo, const float* xin, const float* lam, const float* rho,
-                      float* out, void* ws, void* hist, hipStream_t s) {
-    const long long P = d.B * d.C;
-    const bool train = hist != nullptr;
-    const Hist Hs = make_hist(d);
-    auto ha = [&](int k, int comp) -> float* {  // a_k image (k >= 1), comp 0 = x, 1 = y
-        return reinterpret_cast<float*>(static_cast<char*>(hist) + (size_t)(2 * (k - 1) + comp) * Hs.a_slot);
-    };
-    auto hn = [&](int k) -> float* {  // N_k (k >= 1)
-        return reinterpret_cast<float*>(static_cast<char*>(hist) + Hs.n_off + (size_t)(k - 1) * Hs.n_slot);
-    };
-    const int H = (int)d.H, W = (int)d.W, N = W / 2;
-    cf* twW = at<cf>(ws, Lo.twW);
-    cf* twH = at<cf>(ws, Lo.twH);
+// ------------------------------------------------------------------ the fused two-pass solvers
+// Power-of-two sizes and smooth sizes (mixed_hw) run one iteration sequence, fused_forward and
+// fused_backward below, each on the backend that launches its kernels: Pow2Ops (RowOps<N>, pass_b) or
+// MixedOps (admm_mixed::*, inside the generic layout's regions).  Whatever differs between the two paths
+// is a backend method or constant (DESIGN.md §7e lists them); every operation returns the library's
+// error code.
+struct FusedOps {  // what both backends launch with: the call's descriptor, layout, workspace and tables
+    const admm_tv_desc& d;
+    const Layout& Lo;
+    void* const ws;
+    const int H, N;
+    cf *const twW, *const twH;
+    FusedOps(const admm_tv_desc& d_, const Layout& L, void* w)
+        : d(d_), Lo(L), ws(w), H((int)d_.H), N((int)d_.W / 2), twW(at<cf>(w, L.twW)), twH(at<cf>(w, L.twH)) {}
+};
+
+struct Pow2Ops : FusedOps {
+    static constexpr bool kPsfGrad = true;  // trains with a PSF gradient: r_k's row spectra in the history
+    float* const fcT;
+    cf* const mT;
+    const bool coop;  // A/B knob of the cooperative row pass (RowOps::pass_a): 0 = the plain kernel
+    const int rev;
+    Pow2Ops(const admm_tv_desc& d_, const Layout& L, void* w)
+        : FusedOps(d_, L, w), fcT(at<float>(w, L.fcT)), mT(at<cf>(w, L.mT)),
+          coop(env_int("ADMM_PASSA_COOP", 1) != 0), rev(env_int("ADMM_PASSA_REV", 0)) {}
+    // every module's planes go through each launch (module = plane / planes per module)
+    int modules_per_pass(int G) const { return G; }
+    // The inference path keeps its internal images (u, b, iso norm maps) in the lane-paired row
+    // layout (16-byte accesses, admm_kernels.hpp ld_row); the training history stays in pixel order.
+    // ADMM_PL=0 for the pixel-order layout (A/B).
+    // Default on for iso (C3 iso 507-514 -> 533-544 it/s) and rows up to 512 (C2 +1 %), off for aniso
+    // rows of 1,024+ where the pixel-order streams measured faster (C3 pass A 1.0355 -> 1.0295 ms, 4
+    // interleaved rounds, profiles/r03_sweep_knobs_c3.txt).
+    bool lane_paired(bool train) const { return !train && env_int("ADMM_PL", (d.iso || d.W < 1024) ? 1 : 0) != 0; }
+    int strip(long long rows, bool aniso_fwd) const { return strip_rows(H, N, rows, aniso_fwd); }
+    int r2c(const float* img, cf* spec, long long rows, hipStream_t s, bool pl = false) const {
+        return with_row(N, [&](auto ops) { return decltype(ops)::r2c(img, spec, twW, rows, s, pl); });
+    }
+    int c2r(const cf* spec, float* img, long long rows, hipStream_t s) const {
+        return with_row(N, [&](auto ops) { return decltype(ops)::c2r(spec, img, twW, rows, s); });
+    }
+    // column pass of np planes, ppm per module, from `in` into `out` (the same buffer, or -- PSF-gradient
+    // training -- r_k's kept spectra); the modules' Wiener factors follow one another from fcT (g0 == 0)
+    int col(const cf* in, cf* out, long long np, long long ppm, int /*g0*/, hipStream_t s) const {
+        return pass_b_oop(H, in, out, fcT, mT, twH, N, (int)np, 0, s, (int)ppm);
+    }
+    int iso_norm(const IsoArgs& a, bool first, bool hist, hipStream_t s, bool pl) const {
+        return with_row(N, [&](auto ops) { return decltype(ops)::iso_norm(a, first, hist, s, pl); });
+    }
+    int pass_a(const PassAArgs& a, bool iso, bool first, bool hist, hipStream_t s, bool pl) const {
+        return with_row(N, [&](auto ops) { return decltype(ops)::pass_a(a, iso, first, hist, s, pl, coop); });
+    }
+    int bwd_iso_q(const BwdIsoArgs& a, bool lastk, hipStream_t s) const {
+        return with_row(N, [&](auto ops) { return decltype(ops)::bwd_iso_q(a, lastk, s); });
+    }
+    int bwd_pass_a(const BwdArgs& a, bool iso, bool lastk, bool firstk, hipStream_t s) const {
+        return with_row(N, [&](auto ops) { return decltype(ops)::bwd_pass_a(a, iso, lastk, firstk, s); });
+    }
+    // b = H_t(xin) through the FFT passes; without a PSF (pl only) b = xin, re-laid out
+    int make_b(const float* xin, float* bb, cf* spec, bool pl, hipStream_t s) const {
+        if (d.kh > 0) return psf_transpose_into(d, Lo, ws, xin, bb, spec, 1, s, pl);
+        return with_row(N, [&](auto ops) { return decltype(ops)::pair(xin, bb, d.B * d.C * H, s); });
+    }
+    // x^_in = H_t^T b^ : the conjugate multiplier (pass B mode 2)
+    int apply_ht_t(const float* bbar, float* gxin, cf* spec, hipStream_t s) const {
+        return psf_transpose_into(d, Lo, ws, bbar, gxin, spec, 2, s);
+    }
+};
+
+struct MixedOps : FusedOps {
+    static constexpr bool kPsfGrad = false;  // Layout::mixed_train excludes it (the generic path's history)
+    const float* const fcM;
+    static constexpr int rev = 0;  // no ADMM_PASSA_REV here
+    MixedOps(const admm_tv_desc& d_, const Layout& L, void* w) : FusedOps(d_, L, w), fcM(at<float>(w, L.fcM)) {}
+    // grouped modules (desc.groups, inference only): one module after another through the iterations, each
+    // with its own Wiener factor, lambda, rho and (iso) norm, sharing b, the tables and the regions
+    int modules_per_pass(int) const { return 1; }
+    bool lane_paired(bool) const { return false; }  // pixel order throughout
+    int strip(long long rows, bool) const { return strip_rows_mixed(H, rows, N); }
+    int r2c(const float* img, cf* spec, long long rows, hipStream_t s, bool = false) const {
+        return hip_code(admm_mixed::r2c(N, img, spec, twW, rows, s), "k_row_r2c_m");
+    }
+    int c2r(const cf* spec, float* img, long long rows, hipStream_t s) const {
+        return hip_code(admm_mixed::c2r(N, spec, img, twW, rows, s), "k_row_c2r_m");
+    }
+    // in place only, one module's planes: module g0's factor
+    int col(const cf* in, cf* out, long long np, long long, int g0, hipStream_t s) const {
+        if (in != out) return fail(ADMM_TV_EUNSUPPORTED, "mixed column pass: in place only");
+        return hip_code(admm_mixed::pass_b(H, out, fcM + (size_t)g0 * (2 * N + 1) * H, twH, N, np, s), "k_pass_b_m");
+    }
+    int iso_norm(const IsoArgs& a, bool first, bool hist, hipStream_t s, bool) const {
+        return hip_code(admm_mixed::iso_norm(N, a, first, hist, s), "k_iso_norm_m");
+    }
+    int pass_a(const PassAArgs& a, bool iso, bool first, bool hist, hipStream_t s, bool) const {
+        return hip_code(admm_mixed::pass_a(N, a, iso, first, hist, s), "k_pass_a_m");
+    }
+    int bwd_iso_q(const BwdIsoArgs& a, bool lastk, hipStream_t s) const {
+        return hip_code(admm_mixed::bwd_iso_q(N, a, lastk, s), "k_bwd_iso_q_m");
+    }
+    int bwd_pass_a(const BwdArgs& a, bool iso, bool lastk, bool firstk, hipStream_t s) const {
+        return hip_code(admm_mixed::bwd_pass_a(N, a, iso, lastk, firstk, s), "k_bwd_pass_a_m");
+    }
+    // b = H_t(xin) into the generic b region on the mixed transforms: row r2c, the column pass with the PSF
+    // multiplier, row c2r (HD: three fast launches in place of the generic transforms' ~1 ms); A/B knob
+    // ADMM_MIXED_BGEN=1: the generic transforms (half spectra as scratch)
+    int make_b(const float* xin, float* bb, cf* spec, bool, hipStream_t s) const {
+        const long long P = d.B * d.C;
+        if (env_int("ADMM_MIXED_BGEN", 0)) return gapply<float>(xin, bb, spec, Lo, ws, d, 1, s);
+        if (int e = r2c(xin, spec, P * H, s)) return e;
+        if (int e = hip_code(admm_mixed::pass_b_cm(H, spec, at<cf>(ws, Lo.mM), twH, N, P, s), "k_pass_b_m<cm>")) return e;
+        return c2r(spec, bb, P * H, s);
+    }
+    // x^_in = H_t^T b^ (the conjugate multiplier, generic transforms)
+    int apply_ht_t(const float* bbar, float* gxin, cf* spec, hipStream_t s) const {
+        return gapply<float>(bbar, gxin, spec, Lo, ws, d, 2, s);
+    }
+};
+
+// The forward solve on a fused backend: b = H_t(xin) once (the reference recomputes it every iteration,
+// deconv.py:104), then the modules' iterations, modules_per_pass of them at a time.  Per pass over modules
+// [g0, g0 + ng): r_1 = rowFFT(b) for each, then per iteration the column pass (column FFT, Wiener factor,
+// column IFFT), [iso: the norm pass, its reduce per module and the cross-rank hook], the row pass; the last
+// iteration ends in the output transform.  spec[0] / spec[1] hold the packed row spectra ping-pong, u[0..3]
+// the u images.
+// hist == nullptr: inference (u ping-pong).  Otherwise training: a_k -> hist slot k-1 (x image at 2(k-1),
+// y image at 2(k-1)+1), N_k -> norm slot k-1, and the last iteration's row pass also runs (a_K is needed
+// by the backward); with a PSF gradient (Hist::keep_t) every r_k's row spectra are kept too, so r_1 goes
+// to the history, the column pass reads r_k from there and the row pass writes r_{k+1} there.
+// (measured and removed: plane chunks kept resident in the Infinity Cache through all iterations, and
+// two plane halves on two streams -- DESIGN.md §9; both no faster at C3)
+template <class B>
+int fused_forward(const B& be, const float* xin, const float* lam, const float* rho, float* out, void* hist,
+                  hipStream_t s) {
+    const admm_tv_desc& d = be.d;
+    const Layout& Lo = be.Lo;
+    void* ws = be.ws;
+    const int H = be.H, N = be.N, W = (int)d.W, G = ngroups_of(d);
+    const long long Pm = d.B * d.C;  // planes of one module
     cf* spec[2] = {at<cf>(ws, Lo.spec[0]), at<cf>(ws, Lo.spec[1])};
     float* u[4] = {at<float>(ws, Lo.u[0]), at<float>(ws, Lo.u[1]), at<float>(ws, Lo.u[2]), at<float>(ws, Lo.u[3])};
-    auto hchk = [&](hipError_t e, const char* what) {
-        return e == hipSuccess ? 0 : fail(ADMM_TV_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
-    const long long rows = P * H;
+    const bool train = hist != nullptr;
+    const HistView<float> hv(d, hist);
+    const bool keep_t = B::kPsfGrad && train && hv.h.keep_t;
+    const bool pl = be.lane_paired(train);
     const float* bimg = xin;
-    {
+    if (d.kh > 0 || pl) {
         ProfScope ps(3, s);
-        if (d.kh > 0) {  // b = H_t(xin) once, into the generic b region
-            float* bb = at<float>(ws, Lo.b);
-            // on the mixed transforms: row r2c, the column pass with the PSF multiplier, row c2r (HD: three
-            // fast launches in place of the generic transforms' ~1 ms); A/B knob ADMM_MIXED_BGEN=1: the
-            // generic transforms (half spectra as scratch)
-            if (env_int("ADMM_MIXED_BGEN", 0)) {
-                if (int e = gapply<float>(xin, bb, spec[0], Lo, ws, d, 1, s)) return e;
-            } else {
-                if (int e = hchk(admm_mixed::r2c(N, xin, spec[0], twW, rows, s), "k_row_r2c_m")) return e;
-                if (int e = hchk(admm_mixed::pass_b_cm(H, spec[0], at<cf>(ws, Lo.mM), twH, N, P, s), "k_pass_b_m<cm>"))
-                    return e;
-                if (int e = hchk(admm_mixed::c2r(N, spec[0], bb, twW, rows, s), "k_row_c2r_m")) return e;
-            }
-            bimg = bb;
-        }
-        if (int e = hchk(admm_mixed::r2c(N, bimg, spec[0], twW, rows, s), "k_row_r2c_m")) return e;  // r_1 = b
+        float* bb = at<float>(ws, Lo.b);
+        if (int e = be.make_b(xin, bb, spec[0], pl, s)) return e;
+        bimg = bb;
     }
-    const int R = strip_rows_mixed(H, rows, N);
-    // grouped modules (desc.groups, inference only): one module after another through the iteration,
-    // each with its own Wiener factor, lambda, rho and (iso) norm, sharing b and the tables
-    const int G = ngroups_of(d);
-    const int gpm = Lo.ngroups / G;  // iso plane groups per module (a group never straddles two)
-    for (int g = 0; g < G; ++g) {
-    const float* fcM = at<float>(ws, Lo.fcM) + (size_t)g * (2 * N + 1) * H;
-    const float* lamg = lam + g;
-    const float* rhog = rho + g;
-    float* outg = out + (size_t)g * P * H * W;
-    if (g > 0) {  // r_1 = b again: the previous module's iterations overwrote it
-        ProfScope ps(3, s);
-        if (int e = hchk(admm_mixed::r2c(N, bimg, spec[0], twW, rows, s), "k_row_r2c_m")) return e;
-    }
-    int cur = 0, uin = 0;
-    for (int it = 1; it <= d.maxit; ++it) {
-        {
-            ProfScope ps(1, s);
-            if (int e = hchk(admm_mixed::pass_b(H, spec[cur], fcM, twH, N, P, s), "k_pass_b_m")) return e;
-        }
-        if (it == d.maxit) {
+    const int ng = be.modules_per_pass(G);
+    const long long np = ng * Pm, rows = np * H;  // planes and rows of a pass
+    const int gpm = Lo.ngroups / G;               // iso plane groups per module (a group never straddles two)
+    const int R = be.strip(rows, !d.iso && !train);
+    for (int g0 = 0; g0 < G; g0 += ng) {
+        const float* lamg = lam + g0;
+        const float* rhog = rho + g0;
+        float* outg = out + (size_t)g0 * Pm * H * W;
+        for (int g = 0; g < ng; ++g) {  // r_1 = b for every module of the pass (the one before overwrote it)
             ProfScope ps(3, s);
-            if (int e = hchk(admm_mixed::c2r(N, spec[cur], outg, twW, rows, s), "k_row_c2r_m")) return e;
-            if (!train) break;
+            cf* t0 = (keep_t ? hv.r(1) : spec[0]) + (size_t)g * Pm * H * N;
+            if (int e = be.r2c(bimg, t0, Pm * H, s, pl)) return e;
         }
-        const bool first = it == 1;
-        const float *uxi, *uyi, *nprev = nullptr;
-        float *uxo, *uyo;
-        if (train) {  // a_{k-1} in, a_k out (u is rebuilt from a in the kernels)
-            uxi = first ? nullptr : ha(it - 1, 0);
-            uyi = first ? nullptr : ha(it - 1, 1);
-            uxo = ha(it, 0);
-            uyo = ha(it, 1);
-            if (d.iso && !first) nprev = hn(it - 1);
-        } else {
-            uxi = u[2 * uin];
-            uyi = u[2 * uin + 1];
-            uxo = u[2 * (1 - uin)];
-            uyo = u[2 * (1 - uin) + 1];
-            if (it == d.maxit - 1) uxo = uyo = nullptr;  // the solve's last row pass writes no u (as run_forward)
+        int cur = 0, uin = 0;  // spec[cur] holds the current r spectra; u[2*uin], u[2*uin+1] = u_x, u_y in
+        for (int it = 1; it <= d.maxit; ++it) {
+            {
+                ProfScope ps(1, s);
+                if (int e = be.col(keep_t ? hv.r(it) : spec[cur], spec[cur], np, Pm, g0, s)) return e;
+            }
+            if (it == d.maxit) {
+                ProfScope ps(3, s);
+                if (int e = be.c2r(spec[cur], outg, rows, s)) return e;
+                if (!train) break;
+            }
+            const bool first = (it == 1);
+            const float *uxi, *uyi, *nprev = nullptr;
+            float *uxo, *uyo;
+            if (train) {  // a_{k-1} in, a_k out (u is rebuilt from a in the kernels)
+                uxi = first ? nullptr : hv.a(it - 1, 0);
+                uyi = first ? nullptr : hv.a(it - 1, 1);
+                uxo = hv.a(it, 0);
+                uyo = hv.a(it, 1);
+                if (d.iso && !first) nprev = hv.n(it - 1);
+            } else {
+                uxi = u[2 * uin];
+                uyi = u[2 * uin + 1];
+                uxo = u[2 * (1 - uin)];
+                uyo = u[2 * (1 - uin) + 1];
+                // the last row pass of the solve: only its r spectra are used (the last column pass and
+                // the output transform follow), so it writes no u (k_pass_a: a null output)
+                if (it == d.maxit - 1) uxo = uyo = nullptr;
+            }
+            const float* nsq = nullptr;
+            if (d.iso) {
+                ProfScope ps(2, s);
+                float* nout = train ? hv.n(it) : at<float>(ws, Lo.nsq);
+                IsoArgs ia{spec[cur], uxi, uyi, nprev, lamg, rhog, at<float>(ws, Lo.part), be.twW, (int)np, H, Lo.ppg,
+                           (long long)ng * gpm * H, Pm};
+                if (int e = be.iso_norm(ia, first, train, s, pl)) return e;
+                const long long n4 = 2LL * H * W / 4;
+                for (int g = 0; g < ng; ++g) {  // each module's norm over its own planes
+                    hipLaunchKernelGGL(k_iso_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
+                                       at<float4>(ws, Lo.part) + (size_t)g * gpm * n4,  // n4 float4 = 2HW floats
+                                       reinterpret_cast<float4*>(nout) + (size_t)g * n4, gpm, n4);
+                    if (int e = launch_check("k_iso_reduce")) return e;
+                }
+                // sharded batch: the per-pixel sums must cover every rank's planes
+                allreduce(d, nout, (size_t)ng * 2 * H * W, s);
+                nsq = nout;
+            }
+            {
+                ProfScope ps(0, s);
+                cf* tout = (keep_t && it < d.maxit) ? hv.r(it + 1) : spec[1 - cur];
+                PassAArgs pa{spec[cur], tout, bimg, uxi, uyi, uxo, uyo, nsq, nprev, lamg, rhog, be.twW, H, R, rows / R, Pm,
+                             be.rev};
+                if (int e = be.pass_a(pa, d.iso != 0, first, train, s, pl)) return e;
+            }
+            cur = 1 - cur;
+            uin = 1 - uin;
         }
-        const float* nsq = nullptr;
-        if (d.iso) {
-            ProfScope ps(2, s);
-            float* nout = train ? hn(it) : at<float>(ws, Lo.nsq);
-            IsoArgs ia{spec[cur], uxi, uyi, nprev, lamg, rhog, at<float>(ws, Lo.part), twW, (int)P, H, Lo.ppg,
-                       (long long)gpm * H, P};
-            if (int e = hchk(admm_mixed::iso_norm(N, ia, first, train, s), "k_iso_norm_m")) return e;
-            const long long n4 = 2LL * H * W / 4;
-            hipLaunchKernelGGL(k_iso_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, at<float4>(ws, Lo.part),
-                               reinterpret_cast<float4*>(nout), gpm, n4);
-            if (int e = launch_check("k_iso_reduce")) return e;
-            allreduce(d, nout, 2ull * H * W, s);  // sharded batch: sums over every rank's planes
-            nsq = nout;
-        }
-        {
-            ProfScope ps(0, s);
-            PassAArgs pa{spec[cur], spec[1 - cur], bimg, uxi, uyi, uxo, uyo, nsq, nprev, lamg, rhog, twW, H, R,
-                         rows / R, P, 0};
-            if (int e = hchk(admm_mixed::pass_a(N, pa, d.iso != 0, first, train, s), "k_pass_a_m")) return e;
-        }
-        cur = 1 - cur;
-        uin = 1 - uin;
-    }
     }
     return 0;
 }
 
-// The forward solver.  hist == nullptr: inference (u ping-pong).  Otherwise training mode:
-// a_k -> hist slot k-1 (x image at 2(k-1), y image at 2(k-1)+1), N_k -> norm slot k-1, and
-// the last iteration's pass A also runs (a_K is needed by the backward).
+// The forward solver.  hist == nullptr: inference; otherwise training mode, the iterates kept in the
+// history (fused_forward, run_forward_gen).
 int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, const float* lam, const float* rho,
                 float* out, void* ws, size_t ws_bytes, void* hist, hipStream_t s) {
     const Layout Lo = make_layout(d);
-    if (!ws || ws_bytes < Lo.total || (reinterpret_cast<uintptr_t>(ws) % kAlign) != 0)
-        return fail(ADMM_TV_EWORKSPACE, "workspace too small or not 256-byte aligned");
+    if (int e = check_workspace(ws, ws_bytes, Lo.total)) return e;
     if (Lo.tr && !hist && d.maxit > 0) {  // the transposed odd-length solve (odd_t_hw)
         const long long P = d.B * d.C;
         const int H = (int)d.H, W = (int)d.W;
@@ -1776,13 +1898,13 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
     }
     const int G = ngroups_of(d);
     const long long Pm = d.B * d.C, P = G * Pm;  // planes of one module, of all modules
-    const int H = (int)d.H, W = (int)d.W, N = W / 2;
+    const int H = (int)d.H, W = (int)d.W;
     const size_t img_bytes = (size_t)P * H * W * sizeof(float);
     if (d.maxit == 0) {
         if (img_bytes) HIPCHK(hipMemsetAsync(out, 0, img_bytes, s));  // the reference returns x = zeros (deconv.py:61,117)
         return 0;
     }
-    if (participate_only(d)) {  // the same reductions as run_forward's iso loop, contributing zeros
+    if (participate_only(d)) {  // the same reductions as the solve's iso loop, contributing zeros
         // (grouped modules at a smooth size: one module's iterations after another, 2HW per reduction)
         const bool by_module = Lo.gen && G > 1;
         const size_t n = (Lo.gen ? 1 : (size_t)G) * 2 * H * W;
@@ -1795,135 +1917,9 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
         return 0;
     }
     if (int e = setup(d, Lo, ws, kern, rho, s)) return e;
-    if (Lo.mixed && (!hist || Lo.mixed_train)) return run_forward_mixed(d, Lo, xin, lam, rho, out, ws, hist, s);
+    if (Lo.mixed && (!hist || Lo.mixed_train)) return fused_forward(MixedOps(d, Lo, ws), xin, lam, rho, out, hist, s);
     if (Lo.gen) return run_forward_gen(d, Lo, xin, lam, rho, out, ws, hist, s);
-    cf* twW = at<cf>(ws, Lo.twW);
-    cf* twH = at<cf>(ws, Lo.twH);
-    float* fcT = at<float>(ws, Lo.fcT);
-    cf* mT = at<cf>(ws, Lo.mT);
-    cf* spec[2] = {at<cf>(ws, Lo.spec[0]), at<cf>(ws, Lo.spec[1])};
-    float* u[4] = {at<float>(ws, Lo.u[0]), at<float>(ws, Lo.u[1]), at<float>(ws, Lo.u[2]), at<float>(ws, Lo.u[3])};
-    const bool train = hist != nullptr;
-    const Hist Hs = make_hist(d);
-    auto ha = [&](int k, int comp) -> float* {  // a_k image (k >= 1), comp 0 = x, 1 = y
-        return reinterpret_cast<float*>(static_cast<char*>(hist) + (size_t)(2 * (k - 1) + comp) * Hs.a_slot);
-    };
-    auto hn = [&](int k) -> float* {  // N_k (k >= 1)
-        return reinterpret_cast<float*>(static_cast<char*>(hist) + Hs.n_off + (size_t)(k - 1) * Hs.n_slot);
-    };
-    const bool keep_t = train && Hs.keep_t;
-    auto ht = [&](int k) -> cf* {  // r_k row spectra (k >= 1), kept for the PSF gradient
-        return reinterpret_cast<cf*>(static_cast<char*>(hist) + Hs.t_off + (size_t)(k - 1) * Hs.t_slot);
-    };
-
-    // The inference path keeps its internal images (u, b, iso norm maps) in the lane-paired row
-    // layout (16-byte accesses, admm_kernels.hpp ld_row); the training history stays in pixel order.
-    // ADMM_PL=0 for the pixel-order layout (A/B).
-    // Default on for iso (C3 iso 507-514 -> 533-544 it/s) and rows up to 512 (C2 +1 %), off for aniso
-    // rows of 1,024+ where the pixel-order streams measured faster (C3 pass A 1.0355 -> 1.0295 ms, 4
-    // interleaved rounds, profiles/r03_sweep_knobs_c3.txt).
-    const bool pl = !train && env_int("ADMM_PL", (d.iso || W < 1024) ? 1 : 0) != 0;
-
-    // b = H_t(xin) once (the reference recomputes it every iteration, deconv.py:104)
-    const float* bimg = xin;
-    if (d.kh > 0) {
-        ProfScope ps(3, s);
-        float* bb = at<float>(ws, Lo.b);
-        if (int e = psf_transpose_into(d, Lo, ws, xin, bb, spec[0], 1, s, pl)) return e;
-        bimg = bb;
-    } else if (pl) {  // b = xin, re-laid out
-        ProfScope ps(3, s);
-        float* bb = at<float>(ws, Lo.b);
-        if (int e = with_row(N, [&](auto ops) { return decltype(ops)::pair(xin, bb, Pm * H, s); })) return e;
-        bimg = bb;
-    }
-    for (int g = 0; g < G; ++g) {  // r_1 = b for every module
-        ProfScope ps(3, s);
-        cf* t0 = (keep_t ? ht(1) : spec[0]) + (size_t)g * Pm * H * N;
-        int e = with_row(N, [&](auto ops) { return decltype(ops)::r2c(bimg, t0, twW, Pm * H, s, pl); });
-        if (e) return e;
-    }
-    // Planes [p0, p0 + np) through all iterations (ppm: planes per module of that range).
-    auto solve_planes = [&](long long p0, long long np, long long ppm, hipStream_t st) -> int {
-    const size_t so = (size_t)p0 * H * N, io = (size_t)p0 * H * W;  // cf / float offsets
-    cf* cspec[2] = {spec[0] + so, spec[1] + so};
-    const long long crows = np * H;
-    const float* cb = bimg + io;
-    float* cout = out + io;
-    const int R = strip_rows(H, N, crows, !d.iso && !hist);
-    // A/B knob of the cooperative row pass (RowOps::pass_a): 0 = the plain kernel
-    const bool coop = env_int("ADMM_PASSA_COOP", 1) != 0;
-
-    int cur = 0, uin = 0;  // spec[cur] holds the current r spectra; u[2*uin], u[2*uin+1] = u_x, u_y in
-    for (int it = 1; it <= d.maxit; ++it) {
-        {
-            ProfScope ps(1, st);
-            // PSF-gradient training keeps r_k's spectrum: the column pass then runs out of place
-            const cf* tin = keep_t ? ht(it) : cspec[cur];
-            if (int e = pass_b_oop(H, tin, cspec[cur], fcT, mT, twH, N, (int)np, 0, st, (int)ppm)) return e;
-        }
-        if (it == d.maxit) {
-            ProfScope ps(3, st);
-            int e = with_row(N, [&](auto ops) { return decltype(ops)::c2r(cspec[cur], cout, twW, crows, st); });
-            if (e) return e;
-            if (!train) break;
-        }
-        const bool first = (it == 1);
-        const float *uxi, *uyi, *nprev = nullptr;
-        float *uxo, *uyo;
-        if (train) {
-            uxi = first ? nullptr : ha(it - 1, 0);
-            uyi = first ? nullptr : ha(it - 1, 1);
-            uxo = ha(it, 0);
-            uyo = ha(it, 1);
-            if (d.iso && !first) nprev = hn(it - 1);
-        } else {
-            uxi = u[2 * uin] + io;
-            uyi = u[2 * uin + 1] + io;
-            uxo = u[2 * (1 - uin)] + io;
-            uyo = u[2 * (1 - uin) + 1] + io;
-            // the last row pass of the solve: only its r spectra are used (the last column pass and
-            // the output transform follow), so it writes no u (k_pass_a: a null output)
-            if (it == d.maxit - 1) uxo = uyo = nullptr;
-        }
-        const float* nsq = nullptr;
-        if (d.iso) {
-            ProfScope ps(2, st);
-            float* nout = train ? hn(it) : at<float>(ws, Lo.nsq);
-            IsoArgs ia{cspec[cur], uxi, uyi, nprev, lam, rho, at<float>(ws, Lo.part), twW, (int)P, H, Lo.ppg,
-                       (long long)Lo.ngroups * H, Pm};
-            int e = with_row(N, [&](auto ops) { return decltype(ops)::iso_norm(ia, first, train, st, pl); });
-            if (e) return e;
-            const long long n4 = 2LL * H * W / 4;
-            const int gpm = Lo.ngroups / G;  // plane groups per module
-            for (int g = 0; g < G; ++g) {     // each module's norm over its own planes
-                hipLaunchKernelGGL(k_iso_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                                   at<float4>(ws, Lo.part) + (size_t)g * gpm * n4,  // n4 float4 = 2HW floats
-                                   reinterpret_cast<float4*>(nout) + (size_t)g * n4, gpm, n4);
-                if ((e = launch_check("k_iso_reduce"))) return e;
-            }
-            // sharded batch: the per-pixel sums must cover every rank's planes
-            allreduce(d, nout, (size_t)G * 2 * H * W, st);
-            nsq = nout;
-        }
-        {
-            ProfScope ps(0, st);
-            cf* tout = (keep_t && it < d.maxit) ? ht(it + 1) : cspec[1 - cur];
-            PassAArgs pa{cspec[cur], tout, cb, uxi, uyi, uxo, uyo, nsq, nprev, lam, rho, twW, H, R, crows / R, ppm,
-                         env_int("ADMM_PASSA_REV", 0)};
-            int e = with_row(N, [&](auto ops) {
-                return decltype(ops)::pass_a(pa, d.iso != 0, first, train, st, pl, coop);
-            });
-            if (e) return e;
-        }
-        cur = 1 - cur;
-        uin = 1 - uin;
-    }
-    return 0;
-    };
-    // (measured and removed: plane chunks kept resident in the Infinity Cache through all iterations, and
-    // two plane halves on two streams -- DESIGN.md §9; both no faster at C3)
-    return solve_planes(0, P, Pm, s);
+    return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, hist, s);
 }
 
 // backward workspace = forward layout + a^ ping-pong (4 images) + b^ + per-iteration partials
@@ -1989,13 +1985,7 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
     const int H = (int)d.H, W = (int)d.W, K = d.maxit;
     const long long npx = P * H * W;
     const long long HW = (long long)H * W;
-    const Hist Hs = make_hist(d);
-    char* hb = static_cast<char*>(const_cast<void*>(hist));
-    auto ha = [&](int k, int comp) -> const T* {
-        return reinterpret_cast<const T*>(hb + (size_t)(2 * (k - 1) + comp) * Hs.a_slot);
-    };
-    auto hn = [&](int k) -> const T* { return reinterpret_cast<const T*>(hb + Hs.n_off + (size_t)(k - 1) * Hs.n_slot); };
-    auto ht = [&](int k) -> const C* { return reinterpret_cast<const C*>(hb + Hs.t_off + (size_t)(k - 1) * Hs.t_slot); };
+    const HistView<T> hv(d, hist);
     const bool psf_grad = gkern != nullptr;
     const int Wh = W / 2 + 1;
     const long long nf = (long long)Wh * H;
@@ -2032,7 +2022,7 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
             if (int e = gcol<T>(spec, xspec, fcT, at<C>(ws, Lo.mT), twH, H, W, P, 0, s, gs, Lo.mm)) return e;
             if (int e = grow_inv<T>(spec, rb, twW, W, rows, s, gs, Lo.mmr)) return e;
             if (psf_grad) {
-                hipLaunchKernelGGL(k_gxspec_acc<T>, fgrid, fblk, 0, s, xspec, ht(k), P, H, Wh, fcT, at<double2>(ws, BL.aacc));
+                hipLaunchKernelGGL(k_gxspec_acc<T>, fgrid, fblk, 0, s, xspec, hv.r(k), P, H, Wh, fcT, at<double2>(ws, BL.aacc));
                 if (int e = launch_check("k_gxspec_acc")) return e;
             }
         }
@@ -2040,13 +2030,13 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
             ProfScope ps(2, s);
             const dim3 grid((unsigned)((HW + 255) / 256)), blk(256);
             if (lastk)
-                hipLaunchKernelGGL((k_giso_q<true, T>), grid, blk, 0, s, rb, ab[2 * ain], ab[2 * ain + 1], ha(k - 1, 0),
-                                   ha(k - 1, 1), rho, q, H, W, P);
+                hipLaunchKernelGGL((k_giso_q<true, T>), grid, blk, 0, s, rb, ab[2 * ain], ab[2 * ain + 1], hv.a(k - 1, 0),
+                                   hv.a(k - 1, 1), rho, q, H, W, P);
             else
-                hipLaunchKernelGGL((k_giso_q<false, T>), grid, blk, 0, s, rb, ab[2 * ain], ab[2 * ain + 1], ha(k - 1, 0),
-                                   ha(k - 1, 1), rho, q, H, W, P);
+                hipLaunchKernelGGL((k_giso_q<false, T>), grid, blk, 0, s, rb, ab[2 * ain], ab[2 * ain + 1], hv.a(k - 1, 0),
+                                   hv.a(k - 1, 1), rho, q, H, W, P);
             if (int e = launch_check("k_giso_q")) return e;
-            hipLaunchKernelGGL(k_iso_tau_partial<T>, dim3(BL.ntp), dim3(256), 0, s, q, hn(k - 1), lam, rho,
+            hipLaunchKernelGGL(k_iso_tau_partial<T>, dim3(BL.ntp), dim3(256), 0, s, q, hv.n(k - 1), lam, rho,
                                tpart + (size_t)(K - k) * BL.ntp, 2LL * HW);
             if (int e = launch_check("k_iso_tau_partial")) return e;
             allreduce(d, reinterpret_cast<float*>(q), 2ull * H * W, s);
@@ -2055,9 +2045,9 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
             ProfScope ps(0, s);
             GBwdArgsT<T> ba{rb, xbuf[xo], bbar,
                         ab[2 * ain], ab[2 * ain + 1], ab[2 * (1 - ain)], ab[2 * (1 - ain) + 1],
-                        ha(k, 0), ha(k, 1),
-                        firstk ? nullptr : ha(k - 1, 0), firstk ? nullptr : ha(k - 1, 1),
-                        (d.iso && !firstk) ? hn(k - 1) : nullptr, q, lam, rho,
+                        hv.a(k, 0), hv.a(k, 1),
+                        firstk ? nullptr : hv.a(k - 1, 0), firstk ? nullptr : hv.a(k - 1, 1),
+                        (d.iso && !firstk) ? hv.n(k - 1) : nullptr, q, lam, rho,
                         part + (size_t)(K - k) * BL.nstrips * 2, H, W, npx};
             if (int e = gbwd(ba, d.iso != 0, lastk, firstk, s)) return e;
         }
@@ -2088,90 +2078,161 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
     return 0;
 }
 
-// ------------------------------------------------------------------ fp64 solves (ADMM_TV_FLAG_F64)
-// The forward of an fp64 solve: run_forward's contract on the generic kernels' double instantiation.
-// training backward at a smooth size (Layout::mixed_train; one module, no PSF gradient): the fused
-// path's reverse sequence (admm_tv_backward) on the mixed transforms -- r^_k = M x^_k by the inference
-// column pass, [iso: Q_{k-1} and its tau^ partial], the reverse row pass; then the scalars, and
-// x^_in = H_t^T b^ through the generic transforms when there is a PSF.
-int run_backward_mixed(const admm_tv_desc& d, const BwdLayout& BL, const float* lam, const float* rho,
-                       const float* gout, const void* hist, float* gxin, float* glam, float* grho, void* ws,
-                       hipStream_t s) {
-    const Layout& Lo = BL.f;
-    const long long P = d.B * d.C;
-    const int H = (int)d.H, W = (int)d.W, N = W / 2, K = d.maxit;
-    const Hist Hs = make_hist(d);
-    const char* hb = static_cast<const char*>(hist);
-    auto ha = [&](int k, int comp) -> const float* {
-        return reinterpret_cast<const float*>(hb + (size_t)(2 * (k - 1) + comp) * Hs.a_slot);
-    };
-    auto hn = [&](int k) -> const float* { return reinterpret_cast<const float*>(hb + Hs.n_off + (size_t)(k - 1) * Hs.n_slot); };
-    auto hchk = [&](hipError_t e, const char* what) {
-        return e == hipSuccess ? 0 : fail(ADMM_TV_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
-    cf* twW = at<cf>(ws, Lo.twW);
-    cf* twH = at<cf>(ws, Lo.twH);
-    const float* fcM = at<float>(ws, Lo.fcM);
+// The training backward on a fused backend: the forward's reverse sequence.  x^_K = gout; per iteration,
+// K down to 1: r^_k = M x^_k by the inference column pass, [iso: Q_{k-1} per module, its tau^ partial and
+// the cross-rank hook], the reverse row pass; then the scalar gradients per module, [PSF gradient: the k x k
+// taps,] [grouped modules: their b^ summed,] and x^_in = H_t^T b^ when there is a PSF.  All modules' planes
+// go through every launch (a backend that trains grouped modules runs them together).
+template <class B>
+int fused_backward(const B& be, const BwdLayout& BL, const float* xin, const float* lam, const float* rho,
+                   const float* gout, const void* hist, float* gxin, float* glam, float* grho, float* gkern,
+                   hipStream_t s) {
+    const admm_tv_desc& d = be.d;
+    const Layout& Lo = be.Lo;
+    void* ws = be.ws;
+    const int H = be.H, N = be.N, W = (int)d.W, K = d.maxit, G = ngroups_of(d);
+    const long long Pm = d.B * d.C, P = G * Pm;  // planes of one module, of all modules
+    const HistView<float> hv(d, hist);
+    const bool psf_grad = B::kPsfGrad && gkern != nullptr;
+    const long long nf = (long long)(N + 1) * H;
+    if (psf_grad) {
+        HIPCHK(hipMemsetAsync(at<double2>(ws, BL.aacc), 0, nf * sizeof(double2), s));
+        HIPCHK(hipMemsetAsync(at<double2>(ws, BL.zacc), 0, nf * sizeof(double2), s));
+    }
     cf* spec[2] = {at<cf>(ws, Lo.spec[0]), at<cf>(ws, Lo.spec[1])};
     float* ab[4] = {at<float>(ws, BL.abar[0]), at<float>(ws, BL.abar[1]), at<float>(ws, BL.abar[2]),
                     at<float>(ws, BL.abar[3])};
-    float* bbar = (d.kh == 0 && gxin) ? gxin : at<float>(ws, BL.bbar);  // no PSF: x^_in = b^
+    // b^ accumulates straight into gxin when there is no PSF and one module (x^_in = b^)
+    float* bbar = (d.kh == 0 && gxin && G == 1) ? gxin : at<float>(ws, BL.bbar);
     double* part = at<double>(ws, BL.part);
     double* tpart = at<double>(ws, BL.tpart);
     float* q = at<float>(ws, BL.q);
     const long long rows = P * H;
-    if (d.iso) HIPCHK(hipMemsetAsync(tpart, 0, (size_t)K * BL.ntp * sizeof(double), s));
-    if (int e = hchk(admm_mixed::r2c(N, gout, spec[0], twW, rows, s), "k_row_r2c_m")) return e;
+    if (d.iso) HIPCHK(hipMemsetAsync(tpart, 0, (size_t)K * G * BL.ntp * sizeof(double), s));
+    if (int e = be.r2c(gout, spec[0], rows, s)) return e;
     int cur = 0, ain = 0;
     for (int k = K; k >= 1; --k) {
+        if (psf_grad) {  // A += fc^2 Re(sum_p conj(X^_k) R_k), before the column pass rewrites X^_k
+            if (int e = xspec(H, spec[cur], hv.r(k), at<cf>(ws, BL.xpart), be.twH, N, (int)P, BL.xppg, s)) return e;
+            hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s,
+                               at<cf>(ws, BL.xpart), BL.xgroups, nf, at<float>(ws, Lo.fcT), at<double2>(ws, BL.aacc));
+            if (int e = launch_check("k_xspec_reduce")) return e;
+        }
         {
             ProfScope ps(1, s);
-            if (int e = hchk(admm_mixed::pass_b(H, spec[cur], fcM, twH, N, P, s), "k_pass_b_m")) return e;
+            if (int e = be.col(spec[cur], spec[cur], P, Pm, 0, s)) return e;
         }
         const bool lastk = (k == K), firstk = (k == 1);
         if (d.iso && !firstk) {
             ProfScope ps(2, s);
-            BwdIsoArgs qa{spec[cur], ab[2 * ain], ab[2 * ain + 1], ha(k - 1, 0), ha(k - 1, 1), rho,
-                          at<float>(ws, Lo.part), twW, (int)P, H, Lo.ppg, (long long)Lo.ngroups * H, P};
-            if (int e = hchk(admm_mixed::bwd_iso_q(N, qa, lastk, s), "k_bwd_iso_q_m")) return e;
+            BwdIsoArgs qa{spec[cur], ab[2 * ain], ab[2 * ain + 1], hv.a(k - 1, 0), hv.a(k - 1, 1), rho,
+                          at<float>(ws, Lo.part), be.twW, (int)P, H, Lo.ppg, (long long)Lo.ngroups * H, Pm};
+            if (int e = be.bwd_iso_q(qa, lastk, s)) return e;
             const long long n4 = 2LL * H * W / 4;
-            // Q and the tau^ partials from this rank's Q (N is already global), then Q over every rank's planes
-            hipLaunchKernelGGL(k_iso_reduce_tau, dim3((unsigned)BL.ntp), dim3(256), 0, s, at<float4>(ws, Lo.part),
-                               reinterpret_cast<float4*>(q), Lo.ngroups, n4, reinterpret_cast<const float4*>(hn(k - 1)),
-                               lam, rho, tpart + (size_t)(K - k) * BL.ntp);
-            if (int e = launch_check("k_iso_reduce_tau")) return e;
-            allreduce(d, q, 2ull * H * W, s);
+            const int gpm = Lo.ngroups / G;
+            for (int g = 0; g < G; ++g) {  // per module: Q over its planes, then its tau^ partial
+                float* qg = q + (size_t)g * 2 * H * W;
+                // Q and the tau^ partials from this rank's Q (the norm N is already global): summing the
+                // ranks' lambda/rho gradients then counts every plane once
+                hipLaunchKernelGGL(k_iso_reduce_tau, dim3((unsigned)BL.ntp), dim3(256), 0, s,
+                                   at<float4>(ws, Lo.part) + (size_t)g * gpm * n4, reinterpret_cast<float4*>(qg), gpm, n4,
+                                   reinterpret_cast<const float4*>(hv.n(k - 1) + (size_t)g * 2 * H * W), lam + g, rho + g,
+                                   tpart + ((size_t)(K - k) * G + g) * BL.ntp);
+                if (int e = launch_check("k_iso_reduce_tau")) return e;
+            }
+            allreduce(d, q, (size_t)G * 2 * H * W, s);  // Q over every rank's planes
         }
         {
             ProfScope ps(0, s);
             BwdArgs ba{spec[cur], spec[1 - cur], bbar,
                        ab[2 * ain], ab[2 * ain + 1], ab[2 * (1 - ain)], ab[2 * (1 - ain) + 1],
-                       ha(k, 0), ha(k, 1),
-                       firstk ? nullptr : ha(k - 1, 0), firstk ? nullptr : ha(k - 1, 1),
-                       (d.iso && !firstk) ? hn(k - 1) : nullptr, q, lam, rho,
-                       part + (size_t)(K - k) * BL.nstrips * 2, twW, H, BL.R, BL.nstrips, P};
-            if (int e = hchk(admm_mixed::bwd_pass_a(N, ba, d.iso != 0, lastk, firstk, s), "k_bwd_pass_a_m")) return e;
+                       hv.a(k, 0), hv.a(k, 1),
+                       firstk ? nullptr : hv.a(k - 1, 0), firstk ? nullptr : hv.a(k - 1, 1),
+                       (d.iso && !firstk) ? hv.n(k - 1) : nullptr, q, lam, rho,
+                       part + (size_t)(K - k) * BL.nstrips * 2, be.twW, H, BL.R, BL.nstrips, Pm};
+            if (int e = be.bwd_pass_a(ba, d.iso != 0, lastk, firstk, s)) return e;
         }
         cur = 1 - cur;
         ain = 1 - ain;
     }
     if (glam && grho) {
-        if (int e = bwd_scalars<float>(part, K, BL.nstrips, BL.nstrips, 0LL, d.iso ? tpart : nullptr, BL.ntp, 1, 0, lam,
-                                       rho, glam, grho, s))
-            return e;
+        const long long spm = BL.nstrips / G;  // strips of one module (module-major planes)
+        for (int g = 0; g < G; ++g) {
+            if (int e = bwd_scalars<float>(part, K, BL.nstrips, spm, (long long)g * spm, d.iso ? tpart : nullptr, BL.ntp, G,
+                                           g, lam + g, rho + g, glam + g, grho + g, s))
+                return e;
+        }
     } else if (glam || grho) {
         return fail(ADMM_TV_EINVAL, "glam and grho must be given together");
     }
-    if (gxin && d.kh > 0)  // x^_in = H_t^T b^ (the conjugate multiplier, generic transforms)
-        if (int e = gapply<float>(bbar, gxin, spec[0], Lo, ws, d, 2, s)) return e;
+    if (psf_grad) {  // Z = sum_p conj(Bbar_p) Xin_p, then the k x k taps
+        if (int e = be.r2c(bbar, spec[0], rows, s)) return e;
+        if (int e = be.r2c(xin, spec[1], rows, s)) return e;
+        if (int e = xspec(H, spec[0], spec[1], at<cf>(ws, BL.xpart), be.twH, N, (int)P, BL.xppg, s)) return e;
+        hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, at<cf>(ws, BL.xpart),
+                           BL.xgroups, nf, nullptr, at<double2>(ws, BL.zacc));
+        if (int e = launch_check("k_xspec_reduce")) return e;
+        hipLaunchKernelGGL(k_psf_grad<float>, dim3(d.kh * d.kw), dim3(256), 0, s, at<double2>(ws, BL.aacc),
+                           at<double2>(ws, BL.zacc), at<double2>(ws, Lo.sigma), d.kh, H, W, gkern, 0.25);
+        if (int e = launch_check("k_psf_grad")) return e;
+    }
+    if (gxin && G > 1) {  // the modules share xin: x^_in collects every module's b^
+        const long long n4 = Pm * H * W / 4;
+        float* sum = d.kh > 0 ? bbar : gxin;  // with a PSF, sum in place (module 0's slot) first
+        hipLaunchKernelGGL(k_sum_modules, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(bbar), reinterpret_cast<float4*>(sum), G, n4);
+        if (int e = launch_check("k_sum_modules")) return e;
+    }
+    if (gxin && d.kh > 0)
+        if (int e = be.apply_ht_t(bbar, gxin, spec[0], s)) return e;
     return 0;
 }
 
+// The backward solver (admm_tv_backward's contract, its descriptor already validated).
+int run_backward(const admm_tv_desc& d, const float* xin, const float* kern, const float* lam, const float* rho,
+                 const float* gout, const void* hist, size_t hist_bytes, float* gxin, float* glam, float* grho,
+                 float* gkern, void* ws, size_t ws_bytes, hipStream_t s) {
+    if ((!gout && !participate_only(d)) || !lam || !rho || (d.kh > 0 && !kern))
+        return fail(ADMM_TV_EINVAL, "null pointer argument");
+    const BwdLayout BL = make_bwd_layout(d);
+    const Layout& Lo = BL.f;
+    if (int e = check_workspace(ws, ws_bytes, BL.total)) return e;
+    const int G = ngroups_of(d);
+    const int H = (int)d.H, W = (int)d.W, K = d.maxit;
+    const size_t img_bytes = (size_t)d.B * d.C * H * W * sizeof(float);  // gxin: one module's planes
+    if (gkern && (d.kh == 0 || !(d.flags & ADMM_TV_FLAG_PSF_GRAD) || (!xin && !participate_only(d))))
+        return fail(ADMM_TV_EINVAL, "gkern needs a PSF, ADMM_TV_FLAG_PSF_GRAD (forward and backward) and xin");
+    if (K == 0) {  // output is identically zero
+        if (gxin) HIPCHK(hipMemsetAsync(gxin, 0, img_bytes, s));
+        if (glam) HIPCHK(hipMemsetAsync(glam, 0, sizeof(float) * G, s));
+        if (grho) HIPCHK(hipMemsetAsync(grho, 0, sizeof(float) * G, s));
+        if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(float) * d.kh * d.kw, s));
+        return 0;
+    }
+    if (participate_only(d)) {  // the same reductions as the iso backward, contributing zeros
+        const size_t n = (size_t)G * 2 * H * W;
+        for (int k = K; k >= 2; --k) {
+            HIPCHK(hipMemsetAsync(at<float>(ws, BL.q), 0, n * sizeof(float), s));
+            allreduce(d, at<float>(ws, BL.q), Lo.gen ? 2ull * H * W : n, s);
+        }
+        if (glam) HIPCHK(hipMemsetAsync(glam, 0, sizeof(float) * G, s));
+        if (grho) HIPCHK(hipMemsetAsync(grho, 0, sizeof(float) * G, s));
+        if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(float) * d.kh * d.kw, s));
+        return 0;
+    }
+    if (!hist || hist_bytes < make_hist(d).total) return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
+    if (int e = setup(d, Lo, ws, kern, rho, s)) return e;
+    if (Lo.mixed_train) return fused_backward(MixedOps(d, Lo, ws), BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, s);
+    if (Lo.gen) return run_backward_gen(d, BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, ws, s);
+    return fused_backward(Pow2Ops(d, Lo, ws), BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, s);
+}
+
+// ------------------------------------------------------------------ fp64 solves (ADMM_TV_FLAG_F64)
+// The forward of an fp64 solve: run_forward's contract on the generic kernels' double instantiation.
 int run_forward_f64(const admm_tv_desc& d, const double* xin, const double* kern, const double* lam,
                     const double* rho, double* out, void* ws, size_t ws_bytes, void* hist, hipStream_t s) {
     const Layout Lo = make_layout(d);
-    if (!ws || ws_bytes < Lo.total || (reinterpret_cast<uintptr_t>(ws) % kAlign) != 0)
-        return fail(ADMM_TV_EWORKSPACE, "workspace too small or not 256-byte aligned");
+    if (int e = check_workspace(ws, ws_bytes, Lo.total)) return e;
     const int H = (int)d.H, W = (int)d.W;
     const size_t img_bytes = (size_t)d.B * d.C * H * W * sizeof(double);
     if (d.maxit == 0) {
@@ -2194,8 +2255,7 @@ int run_backward_f64(const admm_tv_desc& d, const double* xin, const double* ker
                      const double* rho, const double* gout, const void* hist, size_t hist_bytes, double* gxin,
                      double* glam, double* grho, double* gkern, void* ws, size_t ws_bytes, hipStream_t s) {
     const BwdLayout BL = make_bwd_layout(d);
-    if (!ws || ws_bytes < BL.total || (reinterpret_cast<uintptr_t>(ws) % kAlign) != 0)
-        return fail(ADMM_TV_EWORKSPACE, "workspace too small or not 256-byte aligned");
+    if (int e = check_workspace(ws, ws_bytes, BL.total)) return e;
     const int H = (int)d.H, W = (int)d.W, K = d.maxit;
     const size_t img_bytes = (size_t)d.B * d.C * H * W * sizeof(double);
     if (gkern && (d.kh == 0 || !(d.flags & ADMM_TV_FLAG_PSF_GRAD) || (!xin && !participate_only(d))))
@@ -2261,7 +2321,7 @@ int admm_tv_forward(const admm_tv_desc* dp, const float* xin, const float* kern,
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
-    if (dg.err != hipSuccess) return fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(dg.err));
+    if (int e = dg.check()) return e;
     return run_forward(*dp, xin, kern, lam, rho, out, ws, ws_bytes, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -2284,7 +2344,7 @@ int admm_tv_forward_train(const admm_tv_desc* dp, const float* xin, const float*
     if (dp->maxit > 0 && (!hist || hist_bytes < make_hist(*dp).total))
         return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
-    if (dg.err != hipSuccess) return fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(dg.err));
+    if (int e = dg.check()) return e;
     return run_forward(*dp, xin, kern, lam, rho, out, ws, ws_bytes, dp->maxit > 0 ? hist : nullptr,
                        reinterpret_cast<hipStream_t>(stream));
 }
@@ -2303,152 +2363,10 @@ int admm_tv_backward(const admm_tv_desc* dp, const float* xin, const float* kern
     if (int e = validate(dp)) return e;
     if (int e = grouped_train_check(*dp)) return e;
     if (is_f64(*dp)) return fail(ADMM_TV_EINVAL, "ADMM_TV_FLAG_F64: use admm_tv_backward_f64");
-    const admm_tv_desc d = *dp;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
-    if (dg.err != hipSuccess) return fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(dg.err));
-    if ((!gout && !participate_only(d)) || !lam || !rho || (d.kh > 0 && !kern))
-        return fail(ADMM_TV_EINVAL, "null pointer argument");
-    const BwdLayout BL = make_bwd_layout(d);
-    const Layout& Lo = BL.f;
-    if (!ws || ws_bytes < BL.total || (reinterpret_cast<uintptr_t>(ws) % kAlign) != 0)
-        return fail(ADMM_TV_EWORKSPACE, "workspace too small or not 256-byte aligned");
-    const int G = ngroups_of(d);
-    const long long Pm = d.B * d.C, P = G * Pm;  // planes of one module, of all modules
-    const int H = (int)d.H, W = (int)d.W, N = W / 2, K = d.maxit;
-    const size_t img_bytes = (size_t)Pm * H * W * sizeof(float);  // gxin: one module's planes
-    const bool psf_grad = gkern != nullptr;
-    if (psf_grad && (d.kh == 0 || !(d.flags & ADMM_TV_FLAG_PSF_GRAD) || (!xin && !participate_only(d))))
-        return fail(ADMM_TV_EINVAL, "gkern needs a PSF, ADMM_TV_FLAG_PSF_GRAD (forward and backward) and xin");
-    if (K == 0) {  // output is identically zero
-        if (gxin) HIPCHK(hipMemsetAsync(gxin, 0, img_bytes, s));
-        if (glam) HIPCHK(hipMemsetAsync(glam, 0, sizeof(float) * G, s));
-        if (grho) HIPCHK(hipMemsetAsync(grho, 0, sizeof(float) * G, s));
-        if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(float) * d.kh * d.kw, s));
-        return 0;
-    }
-    if (participate_only(d)) {  // the same reductions as the iso backward below, contributing zeros
-        const size_t n = (size_t)G * 2 * H * W;
-        for (int k = K; k >= 2; --k) {
-            HIPCHK(hipMemsetAsync(at<float>(ws, BL.q), 0, n * sizeof(float), s));
-            allreduce(d, at<float>(ws, BL.q), Lo.gen ? 2ull * H * W : n, s);
-        }
-        if (glam) HIPCHK(hipMemsetAsync(glam, 0, sizeof(float) * G, s));
-        if (grho) HIPCHK(hipMemsetAsync(grho, 0, sizeof(float) * G, s));
-        if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(float) * d.kh * d.kw, s));
-        return 0;
-    }
-    if (!hist || hist_bytes < make_hist(d).total) return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
-    if (int e = setup(d, Lo, ws, kern, rho, s)) return e;
-    if (Lo.mixed_train) return run_backward_mixed(d, BL, lam, rho, gout, hist, gxin, glam, grho, ws, s);
-    if (Lo.gen) return run_backward_gen(d, BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, ws, s);
-    const Hist Hs = make_hist(d);
-    char* hb = static_cast<char*>(const_cast<void*>(hist));
-    auto ha = [&](int k, int comp) -> const float* {
-        return reinterpret_cast<const float*>(hb + (size_t)(2 * (k - 1) + comp) * Hs.a_slot);
-    };
-    auto hn = [&](int k) -> const float* { return reinterpret_cast<const float*>(hb + Hs.n_off + (size_t)(k - 1) * Hs.n_slot); };
-    auto ht = [&](int k) -> const cf* { return reinterpret_cast<const cf*>(hb + Hs.t_off + (size_t)(k - 1) * Hs.t_slot); };
-    const long long nf = (long long)(N + 1) * H;
-    if (psf_grad) {
-        HIPCHK(hipMemsetAsync(at<double2>(ws, BL.aacc), 0, nf * sizeof(double2), s));
-        HIPCHK(hipMemsetAsync(at<double2>(ws, BL.zacc), 0, nf * sizeof(double2), s));
-    }
-    cf* twW = at<cf>(ws, Lo.twW);
-    cf* twH = at<cf>(ws, Lo.twH);
-    float* fcT = at<float>(ws, Lo.fcT);
-    cf* mT = at<cf>(ws, Lo.mT);
-    cf* spec[2] = {at<cf>(ws, Lo.spec[0]), at<cf>(ws, Lo.spec[1])};
-    float* ab[4] = {at<float>(ws, BL.abar[0]), at<float>(ws, BL.abar[1]), at<float>(ws, BL.abar[2]),
-                    at<float>(ws, BL.abar[3])};
-    // b^ accumulates straight into gxin when there is no PSF and one module (x^_in = b^)
-    float* bbar = (d.kh == 0 && gxin && G == 1) ? gxin : at<float>(ws, BL.bbar);
-    double* part = at<double>(ws, BL.part);
-    double* tpart = at<double>(ws, BL.tpart);
-    float* q = at<float>(ws, BL.q);
-    const long long rows = P * H;
-    if (d.iso) HIPCHK(hipMemsetAsync(tpart, 0, (size_t)K * G * BL.ntp * sizeof(double), s));
-    int e = with_row(N, [&](auto ops) { return decltype(ops)::r2c(gout, spec[0], twW, rows, s); });
-    if (e) return e;
-    int cur = 0, ain = 0;
-    for (int k = K; k >= 1; --k) {
-        if (psf_grad) {  // A += fc^2 Re(sum_p conj(X^_k) R_k), before the column pass rewrites X^_k
-            if ((e = xspec(H, spec[cur], ht(k), at<cf>(ws, BL.xpart), twH, N, (int)P, BL.xppg, s))) return e;
-            hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s,
-                               at<cf>(ws, BL.xpart), BL.xgroups, nf, fcT, at<double2>(ws, BL.aacc));
-            if ((e = launch_check("k_xspec_reduce"))) return e;
-        }
-        {
-            ProfScope ps(1, s);
-            if ((e = pass_b(H, spec[cur], fcT, mT, twH, N, (int)P, 0, s, (int)Pm))) return e;
-        }
-        const bool lastk = (k == K), firstk = (k == 1);
-        if (d.iso && !firstk) {
-            ProfScope ps(2, s);
-            BwdIsoArgs qa{spec[cur], ab[2 * ain], ab[2 * ain + 1], ha(k - 1, 0), ha(k - 1, 1), rho,
-                          at<float>(ws, Lo.part), twW, (int)P, H, Lo.ppg, (long long)Lo.ngroups * H, Pm};
-            if ((e = with_row(N, [&](auto ops) { return decltype(ops)::bwd_iso_q(qa, lastk, s); }))) return e;
-            const long long n4 = 2LL * H * W / 4;
-            const int gpm = Lo.ngroups / G;
-            for (int g = 0; g < G; ++g) {  // per module: Q over its planes, then its tau^ partial
-                float* qg = q + (size_t)g * 2 * H * W;
-                // Q and the tau^ partials from this rank's Q (the norm N is already global): summing the
-                // ranks' lambda/rho gradients then counts every plane once
-                hipLaunchKernelGGL(k_iso_reduce_tau, dim3((unsigned)BL.ntp), dim3(256), 0, s,
-                                   at<float4>(ws, Lo.part) + (size_t)g * gpm * n4, reinterpret_cast<float4*>(qg), gpm, n4,
-                                   reinterpret_cast<const float4*>(hn(k - 1) + (size_t)g * 2 * H * W), lam + g, rho + g,
-                                   tpart + ((size_t)(K - k) * G + g) * BL.ntp);
-                if ((e = launch_check("k_iso_reduce_tau"))) return e;
-            }
-            allreduce(d, q, (size_t)G * 2 * H * W, s);
-        }
-        {
-            ProfScope ps(0, s);
-            BwdArgs ba{spec[cur], spec[1 - cur], bbar,
-                       ab[2 * ain], ab[2 * ain + 1], ab[2 * (1 - ain)], ab[2 * (1 - ain) + 1],
-                       ha(k, 0), ha(k, 1),
-                       firstk ? nullptr : ha(k - 1, 0), firstk ? nullptr : ha(k - 1, 1),
-                       (d.iso && !firstk) ? hn(k - 1) : nullptr, q, lam, rho,
-                       part + (size_t)(K - k) * BL.nstrips * 2, twW, H, BL.R, BL.nstrips, Pm};
-            if ((e = with_row(N, [&](auto ops) { return decltype(ops)::bwd_pass_a(ba, d.iso != 0, lastk, firstk, s); })))
-                return e;
-        }
-        cur = 1 - cur;
-        ain = 1 - ain;
-    }
-    if (glam && grho) {
-        const long long spm = BL.nstrips / G;  // strips of one module (module-major planes)
-        for (int g = 0; g < G; ++g) {
-            if ((e = bwd_scalars<float>(part, K, BL.nstrips, spm, (long long)g * spm, d.iso ? tpart : nullptr, BL.ntp, G, g,
-                                        lam + g, rho + g, glam + g, grho + g, s)))
-                return e;
-        }
-    } else if (glam || grho) {
-        return fail(ADMM_TV_EINVAL, "glam and grho must be given together");
-    }
-    if (psf_grad) {  // Z = sum_p conj(Bbar_p) Xin_p, then the k x k taps
-        if ((e = with_row(N, [&](auto ops) { return decltype(ops)::r2c(bbar, spec[0], twW, rows, s); }))) return e;
-        if ((e = with_row(N, [&](auto ops) { return decltype(ops)::r2c(xin, spec[1], twW, rows, s); }))) return e;
-        if ((e = xspec(H, spec[0], spec[1], at<cf>(ws, BL.xpart), twH, N, (int)P, BL.xppg, s))) return e;
-        hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, at<cf>(ws, BL.xpart),
-                           BL.xgroups, nf, nullptr, at<double2>(ws, BL.zacc));
-        if ((e = launch_check("k_xspec_reduce"))) return e;
-        hipLaunchKernelGGL(k_psf_grad<float>, dim3(d.kh * d.kw), dim3(256), 0, s, at<double2>(ws, BL.aacc),
-                           at<double2>(ws, BL.zacc), at<double2>(ws, Lo.sigma), d.kh, H, W, gkern, 0.25);
-        if ((e = launch_check("k_psf_grad"))) return e;
-    }
-    if (gxin && G > 1) {  // the modules share xin: x^_in collects every module's b^
-        const long long n4 = Pm * H * W / 4;
-        float* sum = d.kh > 0 ? bbar : gxin;  // with a PSF, sum in place (module 0's slot) first
-        hipLaunchKernelGGL(k_sum_modules, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
-                           reinterpret_cast<const float4*>(bbar), reinterpret_cast<float4*>(sum), G, n4);
-        if ((e = launch_check("k_sum_modules"))) return e;
-    }
-    if (gxin && d.kh > 0) {
-        // x^_in = H_t^T b^ : the conjugate multiplier (pass B mode 2)
-        if ((e = psf_transpose_into(d, Lo, ws, bbar, gxin, spec[0], 2, s))) return e;
-    }
-    return 0;
+    if (int e = dg.check()) return e;
+    return run_backward(*dp, xin, kern, lam, rho, gout, hist, hist_bytes, gxin, glam, grho, gkern, ws, ws_bytes,
+                        reinterpret_cast<hipStream_t>(stream));
 }
 
 int admm_tv_psf_transpose(const admm_tv_desc* dp, const float* xin, const float* kern, float* out, void* ws,
@@ -2458,7 +2376,7 @@ int admm_tv_psf_transpose(const admm_tv_desc* dp, const float* xin, const float*
     const admm_tv_desc d = *dp;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
-    if (dg.err != hipSuccess) return fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(dg.err));
+    if (int e = dg.check()) return e;
     const Layout Lo = make_layout(d);
     if (!ws || ws_bytes < Lo.total) return fail(ADMM_TV_EWORKSPACE, "workspace too small");
     const long long P = d.B * d.C;
@@ -2486,7 +2404,7 @@ int admm_tv_forward_f64(const admm_tv_desc* dp, const double* xin, const double*
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
-    if (dg.err != hipSuccess) return fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(dg.err));
+    if (int e = dg.check()) return e;
     return run_forward_f64(*dp, xin, kern, lam, rho, out, ws, ws_bytes, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -2500,7 +2418,7 @@ int admm_tv_forward_train_f64(const admm_tv_desc* dp, const double* xin, const d
     if (dp->maxit > 0 && (!hist || hist_bytes < make_hist(*dp).total))
         return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
-    if (dg.err != hipSuccess) return fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(dg.err));
+    if (int e = dg.check()) return e;
     return run_forward_f64(*dp, xin, kern, lam, rho, out, ws, ws_bytes, dp->maxit > 0 ? hist : nullptr,
                            reinterpret_cast<hipStream_t>(stream));
 }
@@ -2513,7 +2431,7 @@ int admm_tv_backward_f64(const admm_tv_desc* dp, const double* xin, const double
     if ((!gout && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
-    if (dg.err != hipSuccess) return fail(ADMM_TV_EHIP, std::string("device of the stream: ") + hipGetErrorString(dg.err));
+    if (int e = dg.check()) return e;
     return run_backward_f64(*dp, xin, kern, lam, rho, gout, hist, hist_bytes, gxin, glam, grho, gkern, ws, ws_bytes,
                             reinterpret_cast<hipStream_t>(stream));
 }

@@ -1,6 +1,6 @@
 // mixed_capi.hip -- launchers of the mixed-radix fused kernels (mixed_kernels.hpp):
 // the plan tables dispatched to their template instances.  The solve itself is orchestrated in
-// admm_capi.hip (run_forward_mixed).
+// admm_capi.hip (fused_forward / fused_backward on its MixedOps backend).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>

@@ -1,5 +1,6 @@
 // mixed_capi.hpp -- launchers of the mixed-radix fused kernels (mixed_kernels.hpp), compiled in their
-// own translation unit (mixed_capi.hip) and called by the solver's orchestration in admm_capi.hip.
+// own translation unit (mixed_capi.hip) and called by the solver's orchestration in admm_capi.hip
+// (its MixedOps backend of fused_forward / fused_backward, and setup).
 // Every launcher returns hipSuccess or the launch error.
 #pragma once
 #include <hip/hip_runtime.h>
