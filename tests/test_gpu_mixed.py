@@ -65,6 +65,44 @@ CASES = [
     ((1, 1, 1080, 1440), ("random", 5), True, 5),        # rows 720 = 12*10*6 over 120 of 128 lanes
     ((1, 1, 1440, 2560), ("gauss:1.5", 9), False, 4),    # QHD: rows 1280 = 8*4*8*5, cols 12*8*15
     ((1, 1, 800, 800), ("motion", 7), True, 6),          # 800-point columns beside 400-point rows
+    # W = 1080 (N = 540, a multiple of 4 and not of 8) beside every column length but 540 (above): the 8-column
+    # plans run k_pass_b_m<H, 4>, with a PSF also its CM variant (b = H_t(xin)); 2048 / 1536 (4 columns) and
+    # 4096 / 2160 (2) keep their own width over 135 / 270 column blocks
+    ((1, 1, 16, 1080), ("gauss:1.5", 5), False, 3),
+    ((1, 1, 32, 1080), None, True, 3),
+    ((1, 1, 64, 1080), ("motion", 5), True, 3),
+    ((1, 1, 128, 1080), None, False, 3),
+    ((1, 1, 256, 1080), ("gauss:1.5", 7), False, 3),
+    ((1, 1, 512, 1080), None, True, 3),
+    ((1, 1, 1024, 1080), ("motion", 7), True, 3),
+    ((1, 1, 2048, 1080), None, False, 2),
+    ((1, 1, 4096, 1080), ("gauss:1.5", 9), False, 2),
+    ((1, 1, 240, 1080), None, True, 3),
+    ((1, 1, 360, 1080), ("gauss:1.5", 5), False, 3),
+    ((1, 1, 480, 1080), None, False, 3),
+    ((1, 1, 600, 1080), ("motion", 9), True, 3),
+    ((1, 1, 720, 1080), None, True, 3),
+    ((1, 1, 768, 1080), ("gauss:2", 9), False, 3),
+    ((1, 1, 800, 1080), None, False, 3),
+    ((1, 1, 960, 1080), ("random", 5), True, 3),
+    ((1, 1, 1080, 1080), None, True, 3),
+    ((1, 1, 1200, 1080), ("motion", 7), False, 3),
+    ((1, 1, 1440, 1080), None, False, 2),
+    ((1, 3, 1536, 1080), ("gauss:1.5", 7), True, 2),     # three planes: the plane pairs of the tile walk and a last single one
+    ((1, 3, 2160, 1080), None, False, 2),
+    # the power-of-two row plans N = 16 ... 128 beside smooth columns
+    ((1, 3, 240, 32), ("gauss:0.7", 3), False, 6),
+    ((2, 1, 240, 32), None, True, 6),
+    ((1, 2, 240, 64), None, False, 6),
+    ((1, 3, 240, 64), ("motion", 5), True, 6),
+    ((1, 2, 240, 128), ("gauss:1.5", 7), False, 6),
+    ((1, 2, 240, 128), None, True, 6),
+    ((1, 1, 360, 256), None, False, 6),
+    ((1, 2, 360, 256), ("motion", 9), True, 6),
+    # three planes where the column pass walks planes in pairs (H >= 1024, under 8 columns a block): one full
+    # group and a partial one, which falls back to plane-major tiles
+    ((3, 1, 2160, 32), ("gauss:1.5", 5), False, 4),
+    ((3, 1, 4096, 480), None, True, 3),
 ]
 
 
