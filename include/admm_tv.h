@@ -108,8 +108,9 @@ const char* admm_tv_build_hash(void);
  *    960, 1080, 1200, 1440, 1536, 2160} or a power of two up to 4096, W/2 even, e.g. 1080x1920,
  *    720x1280, 480x640, 2160x3840, 600x800): admm_tv_forward runs the same fused two-pass iteration
  *    with mixed-radix register transforms (ABI v6), and so do the training forward / backward of
- *    one module without a PSF gradient (with one, or with grouped modules, they run on the generic
- *    kernels, as for 2);
+ *    one module, with or without a PSF gradient (ADMM_TV_FLAG_PSF_GRAD: the history keeps every r_k's
+ *    packed row spectra, 4 B/pixel/iteration, as at power-of-two sizes); grouped modules train on the
+ *    generic kernels, as for 2;
  * 4: an odd row length with a fused row pass instance (W = 481 = 13 * 37, the BSD image width, any H up
  *    to 65,536): admm_tv_forward's aniso solve runs the two-launch iteration -- the generic column pass
  *    and ONE row pass (inverse rows, step, forward rows; prime-factor transforms in LDS, ABI v7) -- iso

@@ -1,6 +1,8 @@
 """Training-path timing: forward with history + native backward (x, lambda, rho gradients).
 
-usage: python tools/bench_grad.py [--config c3|c2|c5fwd] [--maxit N] [--steps K]
+usage: python tools/bench_grad.py [--config c3|c2|c5fwd|hd|p720] [--maxit N] [--steps K] [--learn-psf]
+--learn-psf: the PSF requires grad too (an ADMMDeconv layer's training step: the history keeps every r_k's
+spectra and the backward adds the PSF gradient's cross spectra); the result line then names the path.
 Prints per-kernel-class time (HIP events: 0 row pass, 1 column pass, 2 iso, 3 setup) for the
 forward-train and the backward separately, and the backward's row-pass bandwidth on its
 algorithmic bytes (r^ spectrum 4 + a_k 8 + a_{k-1} 8 + a^ in 8 + a^ out 8 + b^ rw 8 + x^ out 4
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--config", default="c3")
     ap.add_argument("--maxit", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--learn-psf", action="store_true", help="the PSF requires grad (needs a config with a PSF)")
     a = ap.parse_args()
     from admmtor import _native
     from admmtor.eops.deconv import fft_admm_tv
@@ -32,7 +35,10 @@ def main():
     maxit = a.maxit or maxit
     dev = torch.device("cuda:0")
     psf = make_psf(kind, k).to(dev) if k else torch.empty(0, device=dev)
+    if a.learn_psf and not k:
+        ap.error("--learn-psf: config %s has no PSF" % a.config)
     x = blurred_batch(B, C, H, W, psf.cpu(), seed=1, device=dev).requires_grad_(True)
+    psf.requires_grad_(a.learn_psf)
     lam = torch.tensor([0.01], device=dev, requires_grad=True)
     rho = torch.tensor([0.02], device=dev, requires_grad=True)
     cot = torch.randn(x.shape, device=dev)
@@ -47,7 +53,7 @@ def main():
         return t_f, list(ms_f)
 
     step()
-    x.grad = lam.grad = rho.grad = None
+    x.grad = lam.grad = rho.grad = psf.grad = None
     tot = {"fwd": 0.0, "bwd": 0.0}
     kf = [0.0] * 4
     kb = [0.0] * 4
@@ -66,12 +72,14 @@ def main():
             kf[i] += ms_f[i]
             kb[i] += ms_all[i] - ms_f[i]
             nb[i] = cnt_all[i]
-        x.grad = lam.grad = rho.grad = None
+        x.grad = lam.grad = rho.grad = psf.grad = None
     K = a.steps
     npx = B * C * H * W
     bwd_row_ms = kb[0] / K / maxit
+    flags = _native.ADMM_TV_FLAG_PSF_GRAD if a.learn_psf else 0
     print(json.dumps({
-        "config": a.config, "maxit": maxit, "iso": iso,
+        "config": a.config, "maxit": maxit, "iso": iso, "learn_psf": a.learn_psf,
+        "path": _native.path(_native.desc(B, C, H, W, k, iso, maxit, flags=flags), train=True),
         "fwd_ms": tot["fwd"] / K * 1e3, "bwd_ms": tot["bwd"] / K * 1e3,
         "fwd_kernel_ms": [v / K for v in kf], "bwd_kernel_ms": [v / K for v in kb],
         "bwd_row_pass_ms_per_it": bwd_row_ms,

@@ -109,7 +109,7 @@ bool generic_hw(int64_t H, int64_t W) {
 }
 // smooth sizes on the fused two-pass iteration with mixed-radix register transforms (mixed_kernels.hpp,
 // DESIGN.md §7c): W even with a row plan for W / 2, a column plan for H, not both powers of two (those
-// are supported_hw).  Training too (Layout::mixed_train), except with a PSF gradient or grouped modules.
+// are supported_hw).  Training too (Layout::mixed_train), with or without a PSF gradient, except grouped modules.
 // ADMM_MIXED=0 (A/B knob) keeps them on the generic kernels.
 bool mixed_hw(int64_t H, int64_t W) {
     if (supported_hw(H, W) || H < 16 || W < 16 || (W & 1) || H > 4096 || W > 4096) return false;
@@ -163,8 +163,8 @@ struct Layout {
     // here only, so the regions sized below and the kernels launched later always agree)
     MMPlan mm, mmr;
     // mixed-radix fused iteration (mixed_hw; fused_forward on MixedOps): the Wiener factor for its column pass.
-    // mixed_train: training forward / backward on it too (not with a PSF gradient, whose column-spectrum
-    // history is the generic path's)
+    // mixed_train: training forward / backward on it too, one module (mixed_train_hw); with a PSF gradient the
+    // history keeps r_k's packed row spectra, as on the power-of-two path
     bool mixed, mixed_train;
     size_t fcM;
     // fused odd-length row pass (odd_hw, aniso inference): the second half-spectrum buffer of its ping-pong
@@ -193,6 +193,12 @@ admm_tv_desc transposed(const admm_tv_desc& d) {
     return t;
 }
 
+// a training step of this descriptor runs on the mixed-radix fused kernels: fp32, one module, a smooth size
+// (make_layout, make_hist and make_bwd_layout size their regions by it)
+bool mixed_train_hw(const admm_tv_desc& d) {
+    return !is_f64(d) && ngroups_of(d) == 1 && generic_hw(d.H, d.W) && mixed_hw(d.H, d.W);
+}
+
 Layout make_layout(const admm_tv_desc& d) {
     Layout L{};
     const bool f64 = is_f64(d);
@@ -214,7 +220,7 @@ Layout make_layout(const admm_tv_desc& d) {
         L.mmr = mm_plan_row((int)W);
     }
     L.mixed = L.gen && !f64 && mixed_hw(d.H, d.W) && (G == 1 || !(d.flags & ADMM_TV_FLAG_PSF_GRAD));
-    L.mixed_train = L.mixed && G == 1 && !(k > 0 && (d.flags & ADMM_TV_FLAG_PSF_GRAD));
+    L.mixed_train = mixed_train_hw(d);
     L.odd = L.gen && !f64 && G == 1 && !d.iso && odd_hw(d.H, d.W);
     L.ldw = (int)(N + 1);
     if (L.gen && !f64 && L.mm.ok && L.mmr.ok && env_int("ADMM_GEN_PITCH", 1)) L.ldw = (int)((N + 1 + 15) / 16 * 16);
@@ -1408,7 +1414,7 @@ template <class T> int gbwd(const GBwdArgsT<T>& a, bool iso, bool lastk, bool fi
 // history (training) storage: a_k for k = 1..K (x and y images), iso norms N_k
 struct Hist {
     size_t a_slot;     // bytes of one image
-    size_t t_slot;     // bytes of one kept spectrum (fast path: row spectra; generic: 2-D half spectra)
+    size_t t_slot;     // bytes of one kept spectrum (fused paths: packed row spectra; generic: 2-D half spectra)
     size_t n_slot;     // bytes of one norm pair [2][H][W]
     size_t n_off;      // offset of the norm history
     size_t t_off;      // offset of the r_k spectra (PSF gradient only)
@@ -1425,7 +1431,9 @@ Hist make_hist(const admm_tv_desc& d) {
     h.n_off = (size_t)d.maxit * 2 * h.a_slot;
     h.t_off = h.n_off + (size_t)d.maxit * h.n_slot;
     h.keep_t = d.kh > 0 && (d.flags & ADMM_TV_FLAG_PSF_GRAD);
-    h.t_slot = (is_f64(d) || generic_hw(d.H, d.W)) ? up((size_t)d.B * d.C * d.H * (d.W / 2 + 1) * 2 * rs) : h.a_slot;
+    // (generic_hw is true at smooth sizes too: there the mixed-radix path keeps packed row spectra)
+    const bool generic_t = is_f64(d) || (generic_hw(d.H, d.W) && !mixed_train_hw(d));
+    h.t_slot = generic_t ? up((size_t)d.B * d.C * d.H * (d.W / 2 + 1) * 2 * rs) : h.a_slot;
     h.total = h.t_off + (h.keep_t ? (size_t)d.maxit * h.t_slot : 0);
     return h;
 }
@@ -1693,6 +1701,11 @@ struct Pow2Ops : FusedOps {
     int col(const cf* in, cf* out, long long np, long long ppm, int /*g0*/, hipStream_t s) const {
         return pass_b_oop(H, in, out, fcT, mT, twH, N, (int)np, 0, s, (int)ppm);
     }
+    // cross-spectrum partials for the PSF gradient (weighted: the A terms, which k_xspec_reduce weights by
+    // fcT^2 -- fcT is stored / (2HW) here, so no factor is due)
+    int xspec(const cf* U, const cf* V, cf* part, long long P, int ppg, bool /*weighted*/, hipStream_t s) const {
+        return ::xspec(H, U, V, part, twH, N, (int)P, ppg, s);  // the free launcher above
+    }
     int iso_norm(const IsoArgs& a, bool first, bool hist, hipStream_t s, bool pl) const {
         return with_row(N, [&](auto ops) { return decltype(ops)::iso_norm(a, first, hist, s, pl); });
     }
@@ -1717,7 +1730,7 @@ struct Pow2Ops : FusedOps {
 };
 
 struct MixedOps : FusedOps {
-    static constexpr bool kPsfGrad = false;  // Layout::mixed_train excludes it (the generic path's history)
+    static constexpr bool kPsfGrad = true;  // trains with a PSF gradient: r_k's row spectra in the history
     const float* const fcM;
     static constexpr int rev = 0;  // no ADMM_PASSA_REV here
     MixedOps(const admm_tv_desc& d_, const Layout& L, void* w) : FusedOps(d_, L, w), fcM(at<float>(w, L.fcM)) {}
@@ -1732,10 +1745,20 @@ struct MixedOps : FusedOps {
     int c2r(const cf* spec, float* img, long long rows, hipStream_t s) const {
         return hip_code(admm_mixed::c2r(N, spec, img, twW, rows, s), "k_row_c2r_m");
     }
-    // in place only, one module's planes: module g0's factor
+    // one module's planes with module g0's factor, from `in` into `out` (the same buffer, or -- PSF-gradient
+    // training -- r_k's kept spectra)
     int col(const cf* in, cf* out, long long np, long long, int g0, hipStream_t s) const {
-        if (in != out) return fail(ADMM_TV_EUNSUPPORTED, "mixed column pass: in place only");
-        return hip_code(admm_mixed::pass_b(H, out, fcM + (size_t)g0 * (2 * N + 1) * H, twH, N, np, s), "k_pass_b_m");
+        return hip_code(admm_mixed::pass_b(H, in, out, fcM + (size_t)g0 * (2 * N + 1) * H, twH, N, np, s), "k_pass_b_m");
+    }
+    // Cross spectra of two sets of packed row spectra.  They carry the packed transforms' factor 2 each, as on
+    // the power-of-two path, so conj(U) V is 4 times the plain product.  For Z that is k_psf_grad's zscale
+    // 0.25, on both paths.  For A, k_xspec_reduce weights by fcT^2, and fcT at a smooth size holds the generic
+    // scale fc / (HW), not the power-of-two path's fc / (2HW) (spectra_scale; k_fc_mixed halves it into fcM,
+    // which is laid out [ky][kx] and so cannot be fed to the reduce): the missing (1/2)^2 goes on the
+    // partials instead, the kernel's scale 0.25 (a power of two: exact), so that A = fc^2 Re(conj(X^) R) /
+    // (HW)^2 and A_true = (HW)^2 A holds as k_psf_grad expects.
+    int xspec(const cf* U, const cf* V, cf* part, long long P, int ppg, bool weighted, hipStream_t s) const {
+        return hip_code(admm_mixed::xspec(H, U, V, part, twH, N, P, ppg, weighted ? 0.25f : 1.f, s), "k_xspec_m");
     }
     int iso_norm(const IsoArgs& a, bool first, bool hist, hipStream_t s, bool) const {
         return hip_code(admm_mixed::iso_norm(N, a, first, hist, s), "k_iso_norm_m");
@@ -1965,8 +1988,9 @@ BwdLayout make_bwd_layout(const admm_tv_desc& d) {
         const size_t nf = ((size_t)d.W / 2 + 1) * d.H;
         B.xppg = 8;
         B.xgroups = (int)((d.B * d.C + B.xppg - 1) / B.xppg);
-        // fast path: per-plane-group cross-spectrum partials; generic: one 2-D spectrum set
-        B.xpart = take((B.f.gen ? (size_t)d.B * d.C : (size_t)B.xgroups) * nf * 2 * rs);
+        // fused paths: per-plane-group cross-spectrum partials; generic: one 2-D spectrum set
+        const bool generic_x = B.f.gen && !B.f.mixed_train;
+        B.xpart = take((generic_x ? (size_t)d.B * d.C : (size_t)B.xgroups) * nf * 2 * rs);
         B.aacc = take(nf * sizeof(double2));
         B.zacc = take(nf * sizeof(double2));
     }
@@ -2113,7 +2137,7 @@ int fused_backward(const B& be, const BwdLayout& BL, const float* xin, const flo
     int cur = 0, ain = 0;
     for (int k = K; k >= 1; --k) {
         if (psf_grad) {  // A += fc^2 Re(sum_p conj(X^_k) R_k), before the column pass rewrites X^_k
-            if (int e = xspec(H, spec[cur], hv.r(k), at<cf>(ws, BL.xpart), be.twH, N, (int)P, BL.xppg, s)) return e;
+            if (int e = be.xspec(spec[cur], hv.r(k), at<cf>(ws, BL.xpart), P, BL.xppg, true, s)) return e;
             hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s,
                                at<cf>(ws, BL.xpart), BL.xgroups, nf, at<float>(ws, Lo.fcT), at<double2>(ws, BL.aacc));
             if (int e = launch_check("k_xspec_reduce")) return e;
@@ -2168,7 +2192,7 @@ int fused_backward(const B& be, const BwdLayout& BL, const float* xin, const flo
     if (psf_grad) {  // Z = sum_p conj(Bbar_p) Xin_p, then the k x k taps
         if (int e = be.r2c(bbar, spec[0], rows, s)) return e;
         if (int e = be.r2c(xin, spec[1], rows, s)) return e;
-        if (int e = xspec(H, spec[0], spec[1], at<cf>(ws, BL.xpart), be.twH, N, (int)P, BL.xppg, s)) return e;
+        if (int e = be.xspec(spec[0], spec[1], at<cf>(ws, BL.xpart), P, BL.xppg, false, s)) return e;
         hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, at<cf>(ws, BL.xpart),
                            BL.xgroups, nf, nullptr, at<double2>(ws, BL.zacc));
         if (int e = launch_check("k_xspec_reduce")) return e;

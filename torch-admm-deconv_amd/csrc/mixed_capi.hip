@@ -229,7 +229,7 @@ int pass_b_cols(int H, int N) {
     return cols;
 }
 
-hipError_t pass_b(int H, cf* spec, const float* fcM, const cf* twH, int N, long long P, hipStream_t s) {
+hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH, int N, long long P, hipStream_t s) {
     return with_col(H, [&](auto h) {
         constexpr int HH = decltype(h)::value;
         // tile order (planes per group of the walk; pb_tile): plane-major below H = 1024; above, groups of
@@ -250,9 +250,16 @@ hipError_t pass_b(int H, cf* spec, const float* fcM, const cf* twH, int N, long 
                               : CC >= 8   ? (int)std::min<long long>(P, 1 << 30)
                                           : 2;
             const int colblocks = N / CC;
+            if (in != out) {  // out of place: the same tiles and arithmetic, the stores to `out`
+                if (hipError_t e = lds(k_pass_b_m<HH, CC, false, true>, G::lds_bytes())) return e;
+                hipLaunchKernelGGL((k_pass_b_m<HH, CC, false, true>), dim3((unsigned)(P * colblocks)), dim3(G::NT),
+                                   G::lds_bytes(), s, const_cast<cf*>(in), fcM, twH, N, colblocks, order, fpack, nullptr,
+                                   out);
+                return hipGetLastError();
+            }
             if (hipError_t e = lds(k_pass_b_m<HH, CC>, G::lds_bytes())) return e;
             hipLaunchKernelGGL((k_pass_b_m<HH, CC>), dim3((unsigned)(P * colblocks)), dim3(G::NT), G::lds_bytes(), s,
-                               spec, fcM, twH, N, colblocks, order, fpack);
+                               out, fcM, twH, N, colblocks, order, fpack);
             return hipGetLastError();
         };
         // the plan's columns per block, or fewer when N is no multiple of them (e.g. W = 1080 beside the
@@ -282,6 +289,44 @@ hipError_t pass_b_cm(int H, cf* spec, const cf* mM, const cf* twH, int N, long l
             return hipGetLastError();
         };
         constexpr int C0 = MCol<HH>::C;
+        if (N % C0 == 0) return go(std::integral_constant<int, C0>{});
+        if constexpr (C0 > 4) {
+            if (N % 4 == 0) return go(std::integral_constant<int, 4>{});
+        }
+        if constexpr (C0 > 2) {
+            if (N % 2 == 0) return go(std::integral_constant<int, 2>{});
+        }
+        return hipErrorInvalidValue;
+    });
+}
+
+// The cross-spectrum kernel holds two operand sets and one accumulator set (two in column block 0) where the
+// column pass holds one set, so its blocks have at most 512 threads (two waves per SIMD: 256 registers each;
+// the 960 threads of the 1080-point column pass would leave 128 and spill): XspecC<H> is the plan's columns
+// per block, or 4 or 2 of them (DESIGN.md 7c lists each instance's registers)
+template <int H> struct XspecC {
+    static constexpr int C0 = MCol<H>::C, Lc = MCol<H>::Lc;
+    static constexpr int value = C0 * Lc <= 512 ? C0 : (C0 > 4 && 4 * Lc <= 512) ? 4 : 2;
+};
+hipError_t xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N, long long P, int ppg, float scale,
+                 hipStream_t s) {
+    return with_col(H, [&](auto h) {
+        constexpr int HH = decltype(h)::value;
+        auto go = [&](auto cc) {
+            constexpr int CC = decltype(cc)::value;
+            using G = MColG<HH, CC>;
+            const int colblocks = N / CC;
+            const unsigned groups = (unsigned)((P + ppg - 1) / ppg);
+            if (hipError_t e = lds(k_xspec_m<HH, CC, true>, G::lds_bytes())) return e;
+            if (hipError_t e = lds(k_xspec_m<HH, CC, false>, G::lds_bytes())) return e;
+            hipLaunchKernelGGL((k_xspec_m<HH, CC, true>), dim3(groups), dim3(G::NT), G::lds_bytes(), s, U, V, part, twH, N,
+                               colblocks, (int)P, ppg, scale);
+            if (colblocks > 1)
+                hipLaunchKernelGGL((k_xspec_m<HH, CC, false>), dim3(groups * (unsigned)(colblocks - 1)), dim3(G::NT),
+                                   G::lds_bytes(), s, U, V, part, twH, N, colblocks, (int)P, ppg, scale);
+            return hipGetLastError();
+        };
+        constexpr int C0 = XspecC<HH>::value;
         if (N % C0 == 0) return go(std::integral_constant<int, C0>{});
         if constexpr (C0 > 4) {
             if (N % 4 == 0) return go(std::integral_constant<int, 4>{});

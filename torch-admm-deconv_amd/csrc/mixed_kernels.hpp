@@ -18,7 +18,8 @@
 // Power-of-two lengths get the plans of fft_core.hpp's RowCfg (natural layout, same arithmetic), so
 // a power-of-two W with a smooth H (or the reverse) runs here too.
 // Training too: the forward with history (HIST variants) and the reverse passes (k_bwd_pass_a_m,
-// k_bwd_iso_q_m, at the end of this file); with a PSF gradient the generic kernels train.
+// k_bwd_iso_q_m, at the end of this file); with a PSF gradient the column pass runs out of place (r_k stays
+// in the history) and k_xspec_m forms the cross spectra.
 #pragma once
 #include <type_traits>
 
@@ -585,10 +586,14 @@ static __global__ void k_mt_mixed(const cf* __restrict__ mT, cf* __restrict__ mM
 // multiplier mT, pre-halved and row-major: mM[ky][kx], kx in [0, N]; k_mt_mixed), in place of the generic
 // transforms' three launches.  The packed (DC, Nyquist) column then takes complex a, b (as the
 // power-of-two pass B's MODE 1).
-template <int H, int CC, bool CM = false>
+// OOP: out of place -- the tile is read from spec and written to out (the training forward with a PSF gradient
+// reads r_k from the history, which the backward reads again, and writes x^ to the spectrum buffer); the
+// arithmetic is the in-place instance's.  A template parameter, so the in-place instances keep one buffer
+// resource and their code.
+template <int H, int CC, bool CM = false, bool OOP = false>
 __global__ void __launch_bounds__((MColG<H, CC>::NT))
 k_pass_b_m(cf* spec, const float* __restrict__ fcM, const cf* __restrict__ twH_g, int N, int colblocks, int order,
-           int fpack, const cf* __restrict__ mM = nullptr) {
+           int fpack, const cf* __restrict__ mM = nullptr, cf* out = nullptr) {
     using G = MColG<H, CC>;
     constexpr int Lc = G::Lc, Ec = G::Ec, C = G::C, EM = G::EM, NBz = G::NBz, Qz = G::Qz;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -601,6 +606,7 @@ k_pass_b_m(cf* spec, const float* __restrict__ fcM, const cf* __restrict__ twH_g
     pb_tile(xcd_remap(blockIdx.x, gridDim.x), colblocks, order, true, p, cb);
     const int col = cb * C + c;
     const rsrc_t rs = make_rsrc(spec + (size_t)p * H * N, (unsigned)((size_t)H * N * sizeof(cf)));
+    const rsrc_t ro = OOP ? make_rsrc(out + (size_t)p * H * N, (unsigned)((size_t)H * N * sizeof(cf))) : rs;
     const int voff = (t * N + col) * (int)sizeof(cf);
     const int sstep = Lc * N * (int)sizeof(cf);
     ColBuf<C> buf{data + c};
@@ -677,7 +683,117 @@ k_pass_b_m(cf* spec, const float* __restrict__ fcM, const cf* __restrict__ twH_g
     }
     mfft<H, Lc, EM, +1, 1, 1>(v, buf, tw, t, typename MCol<H>::Inv{});
 #pragma unroll
-    for (int j = 0; j < Ec; ++j) bstore_cf(rs, voff, j * sstep, v[j]);
+    for (int j = 0; j < Ec; ++j) bstore_cf(ro, voff, j * sstep, v[j]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// cross spectra for the PSF gradient (k_xspec, admm_backward.hpp, on the mixed column plans):
+// part[g][kx][ky] = scale * sum_{p in plane group g} conj(colFFT(U_p)) colFFT(V_p), kx in [0, N], from two
+// sets of packed row spectra; k_xspec_reduce and k_psf_grad read the partials as they read k_xspec's.
+// One block per (plane group, column block) accumulates its ppg planes in registers.  COL0 is the instance
+// for column block 0, whose column 0 carries (DC, Nyquist) packed: both operands are split there,
+// A = (F + conj F~)/2, B = (F - conj F~)/(2i) with F~[ky] = F[H - ky], and conj(uA) vA goes to kx = 0,
+// conj(uB) vB to kx = N.  The partners come through LDS: once both transforms are done the exchange buffer
+// is free, so column 0's threads park U in column slot 0 and V in column slot 1 (every plan has C >= 2).
+// After the forward schedule the frequencies sit in layout(Rz) (as in k_pass_b_m): register q + Qz k holds
+// ky = t + Lc q + NBz k, valid for t + Lc q < NBz only -- the padding lanes never store.
+// ---------------------------------------------------------------------------------------------
+template <int H, int CC, bool COL0>
+__global__ void __launch_bounds__((MColG<H, CC>::NT))
+k_xspec_m(const cf* __restrict__ U, const cf* __restrict__ V, cf* __restrict__ part, const cf* __restrict__ twH_g,
+          int N, int colblocks, int P, int ppg, float scale) {
+    using G = MColG<H, CC>;
+    constexpr int Lc = G::Lc, Ec = G::Ec, C = G::C, EM = G::EM, NBz = G::NBz, Qz = G::Qz, Rz = G::Rz, NV = Qz * Rz;
+    static_assert(C >= 2, "the column-0 split parks its two operands in two column slots");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    cf* tw = reinterpret_cast<cf*>(smem);
+    cf* data = tw + H;
+    load_tw(tw, twH_g, H);
+    const int tid = threadIdx.x;
+    const int c = tid % C, t = tid / C;
+    const int ncb = COL0 ? 1 : colblocks - 1;
+    const int grp = blockIdx.x / ncb;
+    const int cb = COL0 ? 0 : 1 + (int)(blockIdx.x % ncb);
+    const int col = cb * C + c;
+    ColBuf<C> buf{data + c};
+    cf acc[NV], accn[COL0 ? NV : 1];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) acc[i] = mkc(0.f, 0.f);
+    if constexpr (COL0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) accn[i] = mkc(0.f, 0.f);
+    }
+    __syncthreads();  // twiddles in LDS
+    const int p1 = min(P, (grp + 1) * ppg);
+    for (int p = grp * ppg; p < p1; ++p) {
+        const cf* up = U + ((size_t)p * H + t) * N + col;
+        const cf* vp = V + ((size_t)p * H + t) * N + col;
+        cf u[EM], v[EM];
+#pragma unroll
+        for (int j = 0; j < Ec; ++j) u[j] = up[(size_t)j * Lc * N];
+#pragma unroll
+        for (int j = 0; j < Ec; ++j) v[j] = vp[(size_t)j * Lc * N];
+        // (each exchange of a transform waits for the buffer's readers before it writes: no barrier between)
+        mfft<H, Lc, EM, -1, 1, 1>(u, buf, tw, t, typename MCol<H>::Fwd{});
+        mfft<H, Lc, EM, -1, 1, 1>(v, buf, tw, t, typename MCol<H>::Fwd{});
+        if constexpr (COL0) {
+            const ColBuf<C> bu{data}, bv{data + 1};
+            __syncthreads();  // the last exchange's reads are done
+            if (c == 0) {
+#pragma unroll
+                for (int q = 0; q < Qz; ++q) {
+                    const int vt = t + Lc * q;
+                    if (vt < NBz) {
+#pragma unroll
+                        for (int k = 0; k < Rz; ++k) {
+                            bu.at(vt + NBz * k) = u[q + Qz * k];
+                            bv.at(vt + NBz * k) = v[q + Qz * k];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < Qz; ++q) {
+                const int vt = t + Lc * q;
+#pragma unroll
+                for (int k = 0; k < Rz; ++k) {
+                    const int i = q + Qz * k;
+                    if (c != 0) {
+                        acc[i] = cadd(acc[i], cmulc(v[i], u[i]));
+                    } else if (vt < NBz) {
+                        const int ky = vt + NBz * k;
+                        const int kp = ky == 0 ? 0 : H - ky;
+                        const cf qu = cconj(bu.at(kp)), qv = cconj(bv.at(kp));
+                        const cf ua = mkc(0.5f * (u[i].x + qu.x), 0.5f * (u[i].y + qu.y));
+                        const cf ub = mkc(0.5f * (u[i].y - qu.y), -0.5f * (u[i].x - qu.x));
+                        const cf va = mkc(0.5f * (v[i].x + qv.x), 0.5f * (v[i].y + qv.y));
+                        const cf vb = mkc(0.5f * (v[i].y - qv.y), -0.5f * (v[i].x - qv.x));
+                        acc[i] = cadd(acc[i], cmulc(va, ua));    // conj(uA) vA
+                        accn[i] = cadd(accn[i], cmulc(vb, ub));  // conj(uB) vB
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) acc[i] = cadd(acc[i], cmulc(v[i], u[i]));
+        }
+    }
+    cf* out = part + (size_t)grp * (N + 1) * H;
+#pragma unroll
+    for (int q = 0; q < Qz; ++q) {
+        const int vt = t + Lc * q;
+        if (vt < NBz) {
+#pragma unroll
+            for (int k = 0; k < Rz; ++k) {
+                const int i = q + Qz * k, ky = vt + NBz * k;
+                out[(size_t)col * H + ky] = cscale(acc[i], scale);
+                if constexpr (COL0) {
+                    if (c == 0) out[(size_t)N * H + ky] = cscale(accn[i], scale);
+                }
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
