@@ -369,21 +369,28 @@ template <int N> struct RowOps {
     // the cooperative variant (admm_kernels.hpp k_pass_a COOP): aniso inference at 1,024-pixel rows
     // (sub-groups of one wave; the iso variant of it spills at 3 waves per SIMD and is not built)
     static constexpr bool kCoop = N == 512;
-    template <bool FIRST, bool PL> static void pa_coop(const PassAArgs& a, unsigned nb, hipStream_t s) {
-        if constexpr (kCoop)
-            hipLaunchKernelGGL((k_pass_a<N, false, FIRST, false, PL, true>), dim3(nb), dim3(G::NT), passa_coop_lds<N>(), s, a);
+    // pf: its pipelined form (k_pass_a PF: every row stream loaded a row ahead, 2 waves per SIMD)
+    template <bool FIRST, bool PL> static void pa_coop(const PassAArgs& a, unsigned nb, hipStream_t s, bool pf) {
+        if constexpr (kCoop) {
+            if (pf)
+                hipLaunchKernelGGL((k_pass_a<N, false, FIRST, false, PL, true, true>), dim3(nb), dim3(G::NT), passa_coop_lds<N>(), s, a);
+            else
+                hipLaunchKernelGGL((k_pass_a<N, false, FIRST, false, PL, true>), dim3(nb), dim3(G::NT), passa_coop_lds<N>(), s, a);
+        }
     }
     // coop: launch the cooperative variant where it can run -- whole blocks of SG strips inside one
     // plane (its exchange barriers need every wave of a block), strips of two rows or more
     static int pass_a(const PassAArgs& a, bool iso, bool first, bool hist, hipStream_t s, bool pl = false,
-                      bool coop = false) {
+                      bool coop = false, bool pf = false) {
         const unsigned nb = blocks(a.nstrips);
         const int sel = (iso ? 4 : 0) | (first ? 2 : 0) | (hist ? 1 : 0);
         if (kCoop && coop && !iso && !hist && !a.rev && a.R >= 2 && a.nstrips % G::SG == 0 &&
             (a.H / a.R) % G::SG == 0) {
             static_assert(!kCoop || passa_coop_lds<N>() <= 53 * 1024, "three blocks of the row pass per CU");
-            if (first) pl ? pa_coop<true, true>(a, nb, s) : pa_coop<true, false>(a, nb, s);
-            else pl ? pa_coop<false, true>(a, nb, s) : pa_coop<false, false>(a, nb, s);
+            // (the pipelined kernel addresses a plane through 32-bit buffer offsets)
+            pf = pf && (long long)a.H * N * (long long)sizeof(cf) < (1LL << 31);
+            if (first) pl ? pa_coop<true, true>(a, nb, s, pf) : pa_coop<true, false>(a, nb, s, pf);
+            else pl ? pa_coop<false, true>(a, nb, s, pf) : pa_coop<false, false>(a, nb, s, pf);
             return launch_check("k_pass_a");
         }
         if (pl && !hist) {  // inference: lane-paired images
@@ -686,7 +693,8 @@ int setup(const admm_tv_desc& d, const Layout& Lo, void* ws, const T* kern, cons
 
 int pow2_floor(int v);
 
-int strip_rows(int H, int N, long long rows, bool aniso_fwd = false) {
+// coop: the solve's row pass may run the cooperative kernel (aniso inference, its knob on, no ADMM_PASSA_REV)
+int strip_rows(int H, int N, long long rows, bool aniso_fwd = false, bool coop = false) {
     int R = env_int("ADMM_PASSA_R", 0);
     // A/B knob: a strip must tile H exactly (pass A maps strip -> (plane, first row) by H / R),
     // so an override is rounded down to a power of two in [2, H]; <= 0 selects the rule below
@@ -704,6 +712,12 @@ int strip_rows(int H, int N, long long rows, bool aniso_fwd = false) {
             R = 16;
             want /= 2;
         }
+        // The cooperative row pass at W = 1024 (halo rows shared inside a block, every stream loaded a row
+        // ahead, 2 waves per SIMD): R = 4, interleaved on one MI355X (profiles/r08_ab_env_c3_passa_pipeline.txt)
+        // C3 745.6-749.4 it/s against 729.7-730.7 with R = 8 and 733.6-736.5 with R = 2.  Only where that
+        // kernel launches (RowOps::pass_a: whole blocks of four strips inside a plane; rows is a multiple
+        // of H): the plain kernel keeps R = 8, which measured best for it.
+        if (coop && aniso_fwd && N == 512 && (H / 4) % 4 == 0) R = 4;
         while (R > 2 && rows / R < want) R /= 2;
     }
     if (R > H) R = H;
@@ -1677,9 +1691,11 @@ struct Pow2Ops : FusedOps {
     cf* const mT;
     const bool coop;  // A/B knob of the cooperative row pass (RowOps::pass_a): 0 = the plain kernel
     const int rev;
+    const bool pf;  // A/B knob of the cooperative row pass's pipelined loads: 0 = the kernel without them
     Pow2Ops(const admm_tv_desc& d_, const Layout& L, void* w)
         : FusedOps(d_, L, w), fcT(at<float>(w, L.fcT)), mT(at<cf>(w, L.mT)),
-          coop(env_int("ADMM_PASSA_COOP", 1) != 0), rev(env_int("ADMM_PASSA_REV", 0)) {}
+          coop(env_int("ADMM_PASSA_COOP", 1) != 0), rev(env_int("ADMM_PASSA_REV", 0)),
+          pf(env_int("ADMM_PASSA_PF", 1) != 0) {}
     // every module's planes go through each launch (module = plane / planes per module)
     int modules_per_pass(int G) const { return G; }
     // The inference path keeps its internal images (u, b, iso norm maps) in the lane-paired row
@@ -1689,7 +1705,7 @@ struct Pow2Ops : FusedOps {
     // rows of 1,024+ where the pixel-order streams measured faster (C3 pass A 1.0355 -> 1.0295 ms, 4
     // interleaved rounds, profiles/r03_sweep_knobs_c3.txt).
     bool lane_paired(bool train) const { return !train && env_int("ADMM_PL", (d.iso || d.W < 1024) ? 1 : 0) != 0; }
-    int strip(long long rows, bool aniso_fwd) const { return strip_rows(H, N, rows, aniso_fwd); }
+    int strip(long long rows, bool aniso_fwd) const { return strip_rows(H, N, rows, aniso_fwd, coop && !rev); }
     int r2c(const float* img, cf* spec, long long rows, hipStream_t s, bool pl = false) const {
         return with_row(N, [&](auto ops) { return decltype(ops)::r2c(img, spec, twW, rows, s, pl); });
     }
@@ -1710,7 +1726,7 @@ struct Pow2Ops : FusedOps {
         return with_row(N, [&](auto ops) { return decltype(ops)::iso_norm(a, first, hist, s, pl); });
     }
     int pass_a(const PassAArgs& a, bool iso, bool first, bool hist, hipStream_t s, bool pl) const {
-        return with_row(N, [&](auto ops) { return decltype(ops)::pass_a(a, iso, first, hist, s, pl, coop); });
+        return with_row(N, [&](auto ops) { return decltype(ops)::pass_a(a, iso, first, hist, s, pl, coop, pf); });
     }
     int bwd_iso_q(const BwdIsoArgs& a, bool lastk, hipStream_t s) const {
         return with_row(N, [&](auto ops) { return decltype(ops)::bwd_iso_q(a, lastk, s); });

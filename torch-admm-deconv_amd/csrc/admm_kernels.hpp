@@ -43,6 +43,8 @@ template <int N, class Cfg = RowCfg<N>> struct RowXf {
 
     // packed spectrum (== 2*rfft of a real row y) -> pixel pairs (2W * y).
     // tw: exp(-2 pi i k / W), k in [0, W)  (LDS)
+    // (SYNC: the exchanges' ordering, fft_core.hpp xsync; 3 keeps global accesses in flight across them)
+    template <int SYNC = 0>
     __device__ __forceinline__ static void c2r(cf (&v)[E], const RowBuf& buf, const cf* __restrict__ tw, int t) {
         cf p[E];
         partner(v, p, t);
@@ -60,12 +62,13 @@ template <int N, class Cfg = RowCfg<N>> struct RowXf {
             }
             v[j] = z;
         }
-        fft_e<N, L, E, +1, 0, 2>(v, buf, tw, t, typename Cfg::S{});
+        fft_e<N, L, E, +1, SYNC, 2>(v, buf, tw, t, typename Cfg::S{});
     }
 
     // pixel pairs of a real row r -> packed spectrum 2*rfft(r)
+    template <int SYNC = 0>
     __device__ __forceinline__ static void r2c(cf (&v)[E], const RowBuf& buf, const cf* __restrict__ tw, int t) {
-        fft_e<N, L, E, -1, 0, 2>(v, buf, tw, t, typename Cfg::S{});
+        fft_e<N, L, E, -1, SYNC, 2>(v, buf, tw, t, typename Cfg::S{});
         cf p[E];
         partner(v, p, t);
 #pragma unroll
@@ -241,6 +244,38 @@ template <int E, int L, bool PL, bool NT> __device__ __forceinline__ void st_row
     } else {
 #pragma unroll
         for (int j = 0; j < E; ++j) st_pol<NT>(&row[t + L * j], v[j]);
+    }
+}
+
+// The same rows through a buffer resource (fft_core.hpp make_rsrc): voff is the lane's byte offset in the
+// row (t * 16 lane-paired, t * 8 in pixel order), soff the row's byte offset in the resource
+// (wave-uniform).  AUX: the cache policy bits (2 = nt).  The hardware checks voff + the constant part
+// against the resource size: a load past it returns zeros without a memory access.
+template <int E, int L, bool PL, int AUX> __device__ __forceinline__ void bld_row(rsrc_t r, int voff, int soff, cf (&v)[E]) {
+    if constexpr (PL) {
+        static_assert(E % 2 == 0, "lane-paired rows need an even number of values per lane");
+#pragma unroll
+        for (int j = 0; j < E / 2; ++j) {
+            const f4v q = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(r, voff + L * j * 16, soff, AUX));
+            v[2 * j] = mkc(q.x, q.y);
+            v[2 * j + 1] = mkc(q.z, q.w);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < E; ++j) v[j] = bload_cf<AUX>(r, voff + L * j * 8, soff);
+    }
+}
+template <int E, int L, bool PL, int AUX> __device__ __forceinline__ void bst_row(rsrc_t r, int voff, int soff, const cf (&v)[E]) {
+    if constexpr (PL) {
+        typedef decltype(__builtin_amdgcn_raw_buffer_load_b128(r, 0, 0, 0)) V4;
+#pragma unroll
+        for (int j = 0; j < E / 2; ++j) {
+            const f4v q = {v[2 * j].x, v[2 * j].y, v[2 * j + 1].x, v[2 * j + 1].y};
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(V4, q), r, voff + L * j * 16, soff, AUX);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < E; ++j) bstore_cf<AUX>(r, voff + L * j * 8, soff, v[j]);
     }
 }
 
@@ -665,12 +700,31 @@ __device__ __forceinline__ cf prev_u(const cf* __restrict__ src, const cf* __res
 template <int N> constexpr size_t passa_coop_lds() {
     return RowKernelGeom<N>::lds_bytes() + sizeof(cf) * (RowKernelGeom<N>::SG - 1) * N;
 }
-template <int N, bool ISO, bool FIRST, bool HIST, bool PL, bool COOP = false>
-__global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
+//
+// PF (the pipelined cooperative variant): a wave walks its strip one row after the other, and every
+// row step needs four row streams from HBM (the x spectrum row, u_y, b, u_x) one after the other, each
+// a full memory round trip with nothing to cover it.  With PF each stream's next row is requested as
+// soon as the current one has been consumed, into the registers that just became free (64 VGPRs
+// more in flight: 202 VGPRs, so the kernel runs at 2 waves per SIMD), so a row's data has a whole row
+// step to arrive.  Each load is issued ahead of the stores of its part of the step (gfx9's vmcnt counts loads
+// and stores in one order, so a wait for a load is also a wait for every store issued before it), all
+// streams go through per-plane buffer resources, and the transforms' exchanges fence LDS only
+// (xsync<3>), so the waits the compiler places are counted ones that leave the younger requests
+// outstanding.  The step after the strip's last one does not exist: its loads are issued all the
+// same, with offsets past the resource's end, which the hardware answers with zeros without touching
+// memory, so every step issues the same operations.  One register set serves: a stream's registers
+// are reloaded right after their last use (the x row is copied into the transform's registers first), so
+// the loop needs no unrolling by two to alternate sets.  The arithmetic of ydirP / finishP / xdirP repeats
+// that of ydir / finish / xdir below: sharing it through helpers changed the code the compiler makes for
+// the 90 other instantiations of this kernel, which stay as they are.  Same operands in the same order:
+// bit-identical (tests/test_gpu_passa_pipeline.py compares the two forms).
+template <int N, bool ISO, bool FIRST, bool HIST, bool PL, bool COOP = false, bool PF = false>
+__global__ void __launch_bounds__(256, PF ? 2 : PASSA_MINW(N)) k_pass_a(PassAArgs a) {
     static_assert(!(PL && HIST), "the training history keeps the pixel-order layout");
     using G = RowKernelGeom<N>;
     constexpr int E = G::E, L = G::L, W = G::W, SG = G::SG;
     static_assert(!COOP || (L == 64 && SG % 2 == 0 && !HIST && !ISO), "cooperative strips: whole waves in pairs, aniso inference");
+    static_assert(!PF || COOP, "the pipelined row step is built for the cooperative walk");
     constexpr bool kSpecNT = (ADMM_NT & 2) != 0 || ((ADMM_NT & 32) != 0 && N >= 512);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     cf* tw = reinterpret_cast<cf*>(smem);
@@ -875,6 +929,172 @@ __global__ void __launch_bounds__(256, PASSA_MINW(N)) k_pass_a(PassAArgs a) {
     if constexpr (!COOP) {
         xrow((i0 - 1 + H) & (H - 1), xprev);
         for (int rr = 0; rr <= R; ++rr) step(false, (i0 + rr) & (H - 1), rr < R, rr >= 1, rr < R);
+    } else if constexpr (PF) {
+        // The cooperative walk below with every stream loaded a row ahead (see the kernel's header).
+        constexpr int kRowB = N * (int)sizeof(cf);  // bytes of a row, spectrum and image alike
+        constexpr int kAuxS = kSpecNT ? 2 : 0, kAuxU = (ADMM_NT & 16) != 0 ? 2 : 0, kAuxW = (ADMM_NT & 1) != 0 ? 2 : 0;
+        const unsigned pB = (unsigned)H * (unsigned)kRowB;  // bytes of a plane (the host admits H N 8 < 2^31)
+        const rsrc_t rsi = make_rsrc(sp, pB), rso = make_rsrc(so, pB), rbb = make_rsrc(bimg, pB);
+        const rsrc_t ruxi = make_rsrc(uxi, pB), ruyi = make_rsrc(uyi, pB);
+        // Every memory operation below is issued by every wave on every path, so the waits the compiler
+        // counts are the same whichever way a step was reached (where paths differ in what they issued, it
+        // must wait as on the shortest, and a wait at the loop's top then covered the u_x loads just
+        // issued).  What a wave must not load or store gets offsets past its resource's end instead: the
+        // hardware drops such a store and answers such a load with zeros.  Without a u output (ust false)
+        // the two output resources are empty (and based on the plane's r spectra, which this wave writes).
+        const rsrc_t ruxo = make_rsrc(ust ? (void*)uxo : (void*)so, ust ? pB : 0u);
+        const rsrc_t ruyo = make_rsrc(ust ? (void*)uyo : (void*)so, ust ? pB : 0u);
+        const int v8 = t * 8, vu = t * (PL ? 16 : 8);  // a lane's byte offset in a spectrum row, an image row
+        // the rows in flight: the next x spectrum row, u_y, b, u_x of the coming step
+        cf px[E], puy[E], pb[E], pux[E];
+        // dead: a row that no step will use -- every offset lies past the resource's end.  The plane size goes
+        // into the per-lane offset on purpose: the hardware checks only that offset (plus the instruction's
+        // constant) against the resource size, never the scalar row offset, so adding it to soff instead
+        // would turn the dropped accesses into real ones outside the plane.
+        auto ldx = [&](int g, bool dead) __attribute__((always_inline)) {
+            bld_row<E, L, false, kAuxS>(rsi, v8 + (dead ? (int)pB : 0), g * kRowB, px);
+        };
+        auto lduy = [&](int g, bool dead) __attribute__((always_inline)) {
+            if constexpr (!FIRST) bld_row<E, L, PL, kAuxU>(ruyi, vu + (dead ? (int)pB : 0), g * kRowB, puy);
+        };
+        auto ldb = [&](int g) __attribute__((always_inline)) { bld_row<E, L, PL, kAuxU>(rbb, vu, g * kRowB, pb); };
+        auto ldux = [&](int g, bool dead) __attribute__((always_inline)) {
+            if constexpr (!FIRST) bld_row<E, L, PL, kAuxU>(ruxi, vu + (dead ? (int)pB : 0), g * kRowB, pux);
+        };
+        using More = std::true_type;
+        using Done = std::false_type;
+        auto pick = [](bool c, cf p, cf q) __attribute__((always_inline)) { return mkc(c ? p.x : q.x, c ? p.y : q.y); };
+        cf xprev[E], xcur[E], wxp[E], wyp[E], wyc[E];
+        // x of the row in flight (-> x), then the request for row gnext
+        auto xrowP = [&](cf (&x)[E], int gnext, bool dead) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) x[j] = px[j];
+            ldx(gnext, dead);
+            RowXf<N>::template c2r<3>(x, buf, tw, t);
+        };
+        // ydir of row gy, the lower of the two rows in hand (the expressions of ystep / ydir above)
+        auto ydirP = [&](bool up, int gy, bool store, auto more, int gnext, bool dead) __attribute__((always_inline)) {
+            cf uy[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const cf xg = pick(up, xprev[j], xcur[j]), xup = pick(up, xcur[j], xprev[j]);
+                const cf u0 = FIRST ? mkc(0.f, 0.f) : puy[j];
+                const float a0 = (xg.x - xup.x) + u0.x;
+                const float a1 = (xg.y - xup.y) + u0.y;
+                const float z0 = shrink_z<false>(a0, tau, 0.f);
+                const float z1 = shrink_z<false>(a1, tau, 0.f);
+                const float n0 = a0 - z0, n1 = a1 - z1;  // u_y(new)
+                uy[j] = mkc(n0, n1);
+                wyc[j] = mkc(z0 - n0, z1 - n1);
+            }
+            if constexpr (decltype(more)::value) lduy(gnext, dead);
+            bst_row<E, L, PL, kAuxW>(ruyo, vu + (store ? 0 : (int)pB), gy * kRowB, uy);
+        };
+        // finish of row gm (fstep / finish above)
+        auto finishP = [&](bool up, int gm, auto more, int gnext) __attribute__((always_inline)) {
+            cf r[E], sh[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) sh[j].x = __shfl(wxp[j].x, (t + 1) & (L - 1), L);
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const cf wa = pick(up, wyc[j], wyp[j]), wb = pick(up, wyp[j], wyc[j]);
+                const float wr = (t == L - 1) ? sh[(j + 1) & (E - 1)].x : sh[j].x;  // w_x at pixel q1+1
+                const float v0 = (wxp[j].x - wxp[j].y) + (wa.x - wb.x);
+                const float v1 = (wxp[j].y - wr) + (wa.y - wb.y);
+                r[j] = mkc(fmaf(rho, v0, pb[j].x), fmaf(rho, v1, pb[j].y));
+            }
+            if constexpr (decltype(more)::value) ldb(gnext);
+            RowXf<N>::template r2c<3>(r, buf, tw, t);
+#pragma unroll
+            for (int j = 0; j < E; ++j) bstore_cf<kAuxW>(rso, v8 + L * j * 8, gm * kRowB, r[j]);
+        };
+        // xdir of row g (xdir above)
+        auto xdirP = [&](int g, int gnext, bool dead) __attribute__((always_inline)) {
+            cf ux[E], sh[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) sh[j].x = __shfl(xcur[j].y, (t - 1) & (L - 1), L);
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const cf u0 = FIRST ? mkc(0.f, 0.f) : pux[j];
+                const float xl = (t == 0) ? sh[(j - 1) & (E - 1)].x : sh[j].x;  // x at pixel q0-1
+                const float a0 = (xcur[j].x - xl) + u0.x;
+                const float a1 = (xcur[j].y - xcur[j].x) + u0.y;
+                const float z0 = shrink_z<false>(a0, tau, 0.f);
+                const float z1 = shrink_z<false>(a1, tau, 0.f);
+                const float n0 = a0 - z0, n1 = a1 - z1;
+                ux[j] = mkc(n0, n1);
+                wxp[j] = mkc(z0 - n0, z1 - n1);
+            }
+            ldux(gnext, dead);
+            bst_row<E, L, PL, kAuxW>(ruxo, vu, g * kRowB, ux);
+        };
+        auto shift = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                wyp[j] = wyc[j];
+                xprev[j] = xcur[j];
+            }
+        };
+        cf* mbox = tw + W + SG * RowBuf::slots(N);
+        const bool up = (sgl & 1) != 0, top = sgl == 0, bot = sgl == SG - 1;  // wave-uniform
+        cf* mbs = mbox + (size_t)min(max(up ? sgl : sgl - 1, 0), SG - 2) * N;  // (unused by top / bot)
+        cf* mbe = mbox + (size_t)(up ? sgl - 1 : sgl) * N;
+        auto put = [&](cf* mb, const cf (&v)[E]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) mb[t + L * j] = v[j];
+        };
+        auto get = [&](const cf* mb, cf (&v)[E]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) v[j] = mb[t + L * j];
+        };
+        const int gs = up ? i0 + R - 1 : i0;    // the strip's first row
+        const int g1 = up ? gs - 1 : gs + 1;    // its second (R >= 2)
+        const int gbel = (i0 + R) & (H - 1);    // the row below the strip
+        // the first row of every stream: x of the block's outer halo (top, bot) or of row gs; u_y of the row
+        // a wave handles ahead of the loop (a down-walker's first, the row below the block); b and u_x of row gs
+        ldx(top ? (i0 - 1 + H) & (H - 1) : bot ? gbel : gs, false);
+        lduy(bot ? gbel : gs, up && !bot);
+        ldb(gs);
+        ldux(gs, false);
+        if (top || bot) xrowP(xprev, gs, false);
+        xrowP(xcur, g1, false);
+        if (up && !bot) put(mbs, xcur);
+        lds_barrier();  // 1: x of the row above each odd boundary
+        if (!up && !top) get(mbs, xprev);
+        // a down-walker's first row; the row below the block (its w_y only)
+        if (!up || bot) {
+            ydirP(up, up ? gbel : gs, !up, More{}, up ? gs : g1, false);
+        } else {  // the other up-walkers: the same requests (u_y of the loop's first row, a dropped store)
+            lduy(gs, false);
+            bst_row<E, L, PL, kAuxW>(ruyo, vu + (int)pB, 0, xcur);
+        }
+        if (!up && !top) put(mbs, wyc);
+        lds_barrier();  // 2: w_y of the row below each odd boundary
+        if (up && !bot) get(mbs, wyc);
+        xdirP(gs, g1, false);
+        shift();
+        for (int rr = 1; rr < R; ++rr) {
+            const int g = up ? i0 + R - 1 - rr : i0 + rr;
+            const bool last = rr == R - 1;                     // the step after it is not walked
+            const int gx = (up ? g - 1 + H : g + 1) & (H - 1);  // the next step's row (in the plane also when last)
+            xrowP(xcur, gx, last);
+            const int gn = up ? g + 1 : g;
+            // (upwards the row after the last step's is the even boundary's, i0: used below)
+            ydirP(up, gn, true, More{}, up ? g : gx, !up && last);
+            finishP(up, up ? gn : g - 1, More{}, g);
+            xdirP(g, gx, last);
+            shift();
+        }
+        if (!up) put(mbe, xprev);
+        lds_barrier();  // 3: x of the row above each even boundary
+        if (up) {
+            get(mbe, xcur);
+            ydirP(true, i0, true, Done{}, 0, false);
+            put(mbe, wyc);
+        }
+        lds_barrier();  // 4: w_y of the row below each even boundary
+        if (!up) get(mbe, wyc);
+        finishP(up, up ? i0 : i0 + R - 1, Done{}, 0);
     } else {
         // one mailbox of a row (register layout t + L j) per boundary between two sub-groups: boundary s
         // lies between sub-groups s and s + 1.  Odd boundaries are met at the start of the walks (an

@@ -265,6 +265,12 @@ __device__ __forceinline__ void lds_barrier() {
 template <int SYNC> __device__ __forceinline__ void xsync() {
     if constexpr (SYNC == 2) {
         lds_barrier();
+    } else if constexpr (SYNC == 3) {
+        // SYNC 3: as SYNC 0 (one wave) with the fences on LDS only, so global loads and stores may stay
+        // in flight, and be scheduled, across the exchange (the pipelined row pass, k_pass_a PF)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
     } else if constexpr (SYNC) {
         __syncthreads();
     } else {
