@@ -122,9 +122,14 @@ const char* admm_tv_build_hash(void);
  * 0: unsupported. */
 int admm_tv_supported(int64_t H, int64_t W);
 
-/* The kernel path a solve of `desc` takes (train = 0: admm_tv_forward; 1: admm_tv_forward_train and
- * admm_tv_backward): one of the ADMM_TV_PATH_* codes, or a negative ADMM_TV_E* code for an invalid
- * descriptor.  Host-only (no device call); tests and benchmarks name the path they measured with it. */
+/* The kernel path a solve of `desc` takes: one of the ADMM_TV_PATH_* codes, or a negative ADMM_TV_E*
+ * code for an invalid descriptor.  `train` selects the entry point:
+ *   0: admm_tv_forward;
+ *   1: admm_tv_forward_train and admm_tv_backward;
+ *   2: admm_tv_forward_state: ADMM_TV_PATH_FUSED or ADMM_TV_PATH_MIXED where admm_tv_forward reports
+ *      them, ADMM_TV_PATH_GENERIC at every other size, the odd row lengths included.
+ * Mode 2 also returns the code with which admm_tv_forward_state refuses the descriptor (its "Refused"
+ * list), so the query agrees with the call.  Host-only (no device call); tests and benchmarks name the path they measured with it. */
 #define ADMM_TV_PATH_FUSED 1    /* power-of-two two-pass iteration (admm_kernels.hpp) */
 #define ADMM_TV_PATH_GENERIC 2  /* generic kernels: column pass, row inverse, step + row forward */
 #define ADMM_TV_PATH_MIXED 3    /* smooth-size two-pass iteration (mixed_kernels.hpp) */
@@ -146,6 +151,43 @@ int admm_tv_workspace_size(const admm_tv_desc* desc, size_t* bytes);
 int admm_tv_forward(const admm_tv_desc* desc, const float* xin, const float* kern,
                     const float* lambda_dev, const float* rho_dev, float* out,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------- solver state
+ * The reference's z_x, z_y, u_x, u_y (deconv.py:63-67,111-115): four (B,C,H,W) fp32 NCHW device images,
+ * in image space whatever path the solve takes.  u is the SCALED dual: a caller who continues with another
+ * rho and wants the unscaled dual kept rescales u by rho_old / rho_new first. */
+typedef struct admm_tv_state { float *zx, *zy, *ux, *uy; } admm_tv_state;
+
+/* Workspace bytes needed by admm_tv_forward_state for `desc` (at least admm_tv_workspace_size's). */
+int admm_tv_state_workspace_size(const admm_tv_desc* desc, size_t* bytes);
+
+/* admm_tv_forward from a given state, returning the state it ends in: resume a solve, warm-start the next
+ * frame or tile, test convergence between chunks of iterations.  Runs `maxit` iterations of deconv.py:103-115
+ * starting from state_in (NULL: zeros, the reference's start), writes the last x to `out` and the state after
+ * the last iteration to state_out (NULL: not wanted).  K1 iterations followed by K2 from the returned state
+ * are K1 + K2 iterations.
+ *  - state_in and state_out may name the same buffers (an in-place update): all of state_in is consumed
+ *    before any of state_out is written.  No other overlap between the arguments.
+ *  - maxit == 0: out is zeros (the reference's x), state_out a copy of state_in (zeros when that is NULL).
+ *  - xin, kern, lambda and rho may differ from the call that produced the state: the state is plain (z, u),
+ *    so a new frame or a changed rho is well defined (see admm_tv_state on rescaling u).
+ *  - Conventions as admm_tv_forward: asynchronous, graph-capturable, no host synchronisation, lambda / rho
+ *    read on the device, runs on the stream's device, no per-solve global state.
+ *  - Paths (admm_tv_path(desc, 2)): the fused power-of-two and smooth-size iterations carry the state
+ *    through two streaming kernels at the call's ends (csrc/state_kernels.hpp); every other size runs the
+ *    generic loop.  That includes the odd row lengths (admm_tv_supported == 4, either orientation): the
+ *    odd-length row pass and its transposed wrapper know nothing of state, so a stateful solve there takes
+ *    the generic three-launch iteration, not admm_tv_forward's two.
+ *  - Alignment: the state images, xin and out need only be float-aligned, like admm_tv_forward's arrays;
+ *    16-byte aligned ones (with W a multiple of 4) take the 16-byte accesses.
+ *  - Refused: groups > 1, an all-reduce hook, and more than 2^31 - 1 image rows (B*C*H) in one call
+ *    (ADMM_TV_EUNSUPPORTED; admm_tv_state_workspace_size and admm_tv_path(desc, 2) refuse them alike);
+ *    ADMM_TV_FLAG_F64 and ADMM_TV_FLAG_PSF_GRAD (ADMM_TV_EINVAL); a state struct with a null member
+ *    (ADMM_TV_EINVAL). */
+int admm_tv_forward_state(const admm_tv_desc* desc, const float* xin, const float* kern,
+                          const float* lambda_dev, const float* rho_dev,
+                          const admm_tv_state* state_in, const admm_tv_state* state_out,
+                          float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* fp64 variants (desc->flags must hold ADMM_TV_FLAG_F64; the plain entry points refuse it): the
  * same contracts as admm_tv_forward / admm_tv_forward_train / admm_tv_backward with double arrays. */

@@ -38,6 +38,8 @@ EXPORTED = (
     "admm_tv_path",
     "admm_tv_workspace_size",
     "admm_tv_forward",
+    "admm_tv_state_workspace_size",
+    "admm_tv_forward_state",
     "admm_tv_forward_f64",
     "admm_tv_forward_train_f64",
     "admm_tv_backward_f64",
@@ -83,6 +85,11 @@ class AdmmTvDesc(ctypes.Structure):
         ("allreduce", ALLREDUCE_FN),      # per-call cross-rank hook (iso over a sharded batch)
         ("allreduce_ctx", ctypes.c_void_p),
     ]
+
+
+class AdmmTvState(ctypes.Structure):
+    """admm_tv_state: the reference's z_x, z_y, u_x, u_y as four fp32 (B,C,H,W) device images."""
+    _fields_ = [("zx", ctypes.c_void_p), ("zy", ctypes.c_void_p), ("ux", ctypes.c_void_p), ("uy", ctypes.c_void_p)]
 
 
 ADMM_TV_FLAG_PSF_GRAD = 1
@@ -190,6 +197,11 @@ def _open(path: str) -> ctypes.CDLL:
     for f in ("admm_tv_forward", "admm_tv_forward_f64"):
         getattr(L, f).restype = ctypes.c_int
         getattr(L, f).argtypes = [dp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.admm_tv_state_workspace_size.restype = ctypes.c_int
+    L.admm_tv_state_workspace_size.argtypes = [dp, ctypes.POINTER(sz)]
+    stp = ctypes.POINTER(AdmmTvState)
+    L.admm_tv_forward_state.restype = ctypes.c_int
+    L.admm_tv_forward_state.argtypes = [dp, vp, vp, vp, vp, stp, stp, vp, vp, sz, vp]
     L.admm_tv_history_size.restype = ctypes.c_int
     L.admm_tv_history_size.argtypes = [dp, ctypes.POINTER(sz)]
     for f in ("admm_tv_forward_train", "admm_tv_forward_train_f64"):
@@ -271,10 +283,22 @@ def backward_workspace_size(d: AdmmTvDesc) -> int:
     return int(n.value)
 
 
-def path(d: AdmmTvDesc, train: bool = False) -> str:
+def state_workspace_size(d: AdmmTvDesc) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().admm_tv_state_workspace_size(ctypes.byref(d), ctypes.byref(n)))
+    return int(n.value)
+
+
+def state_of(zx, zy, ux, uy) -> AdmmTvState:
+    """admm_tv_state over four tensors (the caller keeps them alive for the call)."""
+    return AdmmTvState(zx.data_ptr(), zy.data_ptr(), ux.data_ptr(), uy.data_ptr())
+
+
+def path(d: AdmmTvDesc, train: bool = False, mode: int = None) -> str:
     """The kernel path a solve of descriptor `d` takes (admm_tv_path): "fused", "generic",
-    "fused mixed-radix" or "fused odd-length"."""
-    code = load().admm_tv_path(ctypes.byref(d), 1 if train else 0)
+    "fused mixed-radix" or "fused odd-length".  mode (overrides train): 0 admm_tv_forward, 1 the training
+    entry points, 2 admm_tv_forward_state."""
+    code = load().admm_tv_path(ctypes.byref(d), int(mode) if mode is not None else (1 if train else 0))
     if code < 0:
         check(code)
     return PATHS[code]

@@ -7,6 +7,9 @@ graph, with no graph break, and the autograd formula is registered on the op its
 
   admm_hip::fft_admm_tv_fwd(x, lam, rho, kern, iso, maxit) -> out
       inference solve (admm_tv_forward); out has G*B planes for G = lam.numel() modules
+  admm_hip::fft_admm_tv_state(x, lam, rho, kern, state, iso, maxit) -> (out, z_x, z_y, u_x, u_y)
+      the stateful inference solve (admm_tv_forward_state): iterations from `state` (the reference's
+      z_x, z_y, u_x, u_y, or an empty list for zeros), the state afterwards as new tensors
   admm_hip::fft_admm_tv_fwd_train(x, lam, rho, kern, iso, maxit, psf_grad) -> (out, hist)
       the training forward (admm_tv_forward_train): hist is the uint8 history the backward reads
   admm_hip::fft_admm_tv_bwd(gout, x, lam, rho, kern, hist, iso, maxit, psf_grad,
@@ -24,14 +27,14 @@ path keeps the ``autograd.Function`` in ``admmtor._backward`` (first order only)
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Sequence, Tuple
 
 import torch
 from torch import Tensor
 
 from . import _native
 
-__all__ = ["fft_admm_tv_fwd", "fft_admm_tv_fwd_train", "fft_admm_tv_bwd"]
+__all__ = ["fft_admm_tv_fwd", "fft_admm_tv_state", "fft_admm_tv_fwd_train", "fft_admm_tv_bwd"]
 
 
 def _k(kern: Tensor) -> int:
@@ -89,6 +92,41 @@ def fft_admm_tv_fwd(x: Tensor, lam: Tensor, rho: Tensor, kern: Tensor, iso: bool
 def _(x, lam, rho, kern, iso, maxit):
     B, C, H, W = x.shape
     return x.new_empty((lam.shape[0] * B, C, H, W), dtype=x.dtype)
+
+
+# ---------------------------------------------------------------- stateful inference
+@torch.library.custom_op("admm_hip::fft_admm_tv_state", mutates_args=())
+def fft_admm_tv_state(x: Tensor, lam: Tensor, rho: Tensor, kern: Tensor, state: Sequence[Tensor], iso: bool,
+                      maxit: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """admm_tv_forward_state: `maxit` iterations from `state` -- (z_x, z_y, u_x, u_y) shaped like x, or empty
+    for the reference's zero start -- returning (x, z_x, z_y, u_x, u_y) as new tensors.  fp32, one module."""
+    _check_device(x, lam, rho, kern, *state)
+    if x.dtype != torch.float32 or lam.numel() != 1:
+        raise NotImplementedError("admm_hip::fft_admm_tv_state: fp32, one module (lam, rho of one element)")
+    if len(state) not in (0, 4):
+        raise ValueError("admm_hip::fft_admm_tv_state: state is (z_x, z_y, u_x, u_y) or empty")
+    B, C, H, W = x.shape
+    _check_supported(H, W, False)
+    d = _desc(x, lam, kern, iso, maxit)
+    x, lam, rho, kern = x.contiguous(), lam.contiguous(), rho.contiguous(), kern.contiguous()
+    sin = [t.contiguous() for t in state]
+    for t in sin:
+        if t.shape != x.shape or t.dtype != x.dtype or t.device != x.device:
+            raise ValueError("admm_hip::fft_admm_tv_state: every state tensor is fp32, shaped like x, on x's device")
+    ws = torch.empty(_native.state_workspace_size(d), dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(x)
+    sout = [torch.empty_like(x) for _ in range(4)]
+    st_in = _native.state_of(*sin) if sin else None
+    st_out = _native.state_of(*sout)
+    _native.check(_native.load().admm_tv_forward_state(
+        d, x.data_ptr(), kern.data_ptr() if _k(kern) > 0 else None, lam.data_ptr(), rho.data_ptr(),
+        st_in, st_out, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return (out, *sout)
+
+
+@fft_admm_tv_state.register_fake
+def _(x, lam, rho, kern, state, iso, maxit):
+    return tuple(torch.empty_like(x, memory_format=torch.contiguous_format) for _ in range(5))
 
 
 # ---------------------------------------------------------------- training forward + backward

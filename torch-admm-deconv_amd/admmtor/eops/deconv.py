@@ -17,7 +17,7 @@ Drop-in for ``/root/reference/src/admmtor/eops/deconv.py``:
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -34,6 +34,9 @@ __all__ = [
     "identity",
     "conv_circular",
     "fft_admm_tv",
+    "ADMMState",
+    "fft_admm_tv_state",
+    "fft_admm_tv_until",
 ]
 
 
@@ -242,6 +245,93 @@ def _fft_admm_tv_impl(xin, lmbd, rho, kern, iso=False, maxit=100, hook=None) -> 
         out = _solve(xc, kc, _as_device_scalar(lmbd, dev, cdt), _as_device_scalar(rho, dev, cdt), bool(iso), maxit,
                      hook=hook)
     return out.to(device=home, dtype=out_dtype)
+
+
+class ADMMState(NamedTuple):
+    """The solver state between iterations: the reference's ``z_x, z_y, u_x, u_y`` (deconv.py:63-67,
+    111-115), fp32 device tensors shaped like ``xin``.  ``u`` is the scaled dual: to continue with another
+    ``rho`` and keep the unscaled dual, rescale ``u_x, u_y`` by ``rho_old / rho_new`` first."""
+    z_x: torch.Tensor
+    z_y: torch.Tensor
+    u_x: torch.Tensor
+    u_y: torch.Tensor
+
+
+def fft_admm_tv_state(xin: torch.Tensor, lmbd, rho, kern: torch.Tensor, iso: bool = False, maxit: int = 100,
+                      state: Optional[ADMMState] = None) -> Tuple[torch.Tensor, ADMMState]:
+    """:func:`fft_admm_tv` from a given state, returning the state it ends in: ``(x, state)``.
+
+    Runs ``maxit`` iterations of the reference's loop (deconv.py:103-115) starting from ``state`` (``None``:
+    zeros, the reference's start).  ``K1`` iterations followed by ``K2`` from the returned state are
+    ``K1 + K2`` iterations, so a solve can be resumed, the next video frame or a neighbouring tile started
+    from this one's state (``xin``, ``kern``, ``lmbd`` and ``rho`` may change between calls), or convergence
+    tested between chunks (:func:`fft_admm_tv_until`).  ``maxit = 0`` returns zeros and the state unchanged.
+
+    Inference only, fp32, one module: if gradients are enabled and an input requires grad the call raises
+    (``fft_admm_tv`` is the differentiable call); fp64 inputs raise ``NotImplementedError``.  Host inputs are
+    staged to the current ROCm device as in ``fft_admm_tv``; ``x`` comes back on ``xin``'s device, the state
+    stays on the ROCm device.  The returned state never requires grad.
+    """
+    if not isinstance(kern, torch.Tensor):
+        kern = torch.as_tensor(kern)
+    _check_inputs(xin, kern)
+    if xin.dtype == torch.float64:
+        raise NotImplementedError("fft_admm_tv_state: fp32 solves only (fp64 state is not implemented)")
+    if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad
+                                       for v in (xin, lmbd, rho, kern, *(state or ()))):
+        raise RuntimeError("fft_admm_tv_state is inference only: an input requires grad; fft_admm_tv is the "
+                           "differentiable call (or run under torch.no_grad())")
+    home = xin.device
+    maxit = max(0, int(maxit))
+    xin, lmbd, rho, kern = _stage(xin, lmbd, rho, kern)
+    dev = xin.device
+    if state is not None:
+        if len(state) != 4:
+            raise ValueError("state must be ADMMState(z_x, z_y, u_x, u_y)")
+        for name, t in zip(ADMMState._fields, state):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(xin.shape) or t.dtype != torch.float32 \
+                    or t.device != dev:
+                raise ValueError(f"state.{name} must be an fp32 tensor of shape {tuple(xin.shape)} on {dev}")
+    with torch.no_grad():
+        xc = xin.detach().to(torch.float32).contiguous()
+        kc = kern.detach().to(device=dev, dtype=torch.float32).contiguous() if kern.numel() > 0 else \
+            torch.empty(0, dtype=torch.float32, device=dev)
+        sin = [t.detach().contiguous() for t in state] if state is not None else []
+        out, zx, zy, ux, uy = torch.ops.admm_hip.fft_admm_tv_state(
+            xc, _as_device_scalar(lmbd, dev), _as_device_scalar(rho, dev), kc, sin, bool(iso), maxit)
+    return out.to(device=home), ADMMState(zx, zy, ux, uy)
+
+
+def fft_admm_tv_until(xin: torch.Tensor, lmbd, rho, kern: torch.Tensor, iso: bool = False, tol: float = 1e-4,
+                      check_every: int = 10, maxit: int = 100) -> Tuple[torch.Tensor, ADMMState, int]:
+    """ADMM-TV until the iterate stops moving: ``(x, state, iterations)``.
+
+    Runs chunks of ``check_every`` iterations through :func:`fft_admm_tv_state` (the last chunk shorter, so
+    that at most ``maxit`` iterations run) and after each chunk computes ``c = ||x_new - x_prev||_2 /
+    ||x_new||_2`` with torch ops on the ROCm device (``x_prev`` = 0 before the first chunk); stops when
+    ``c <= tol`` or at ``maxit``.  Reading ``c`` is ONE host synchronisation per chunk; the iterations in
+    between stay asynchronous.  Host inputs are staged to the device once, before the first chunk, and ``x``
+    is copied back to ``xin``'s device once, at the end.  The returned state continues the solve
+    (``fft_admm_tv_state(..., state=state)``).
+    """
+    if not isinstance(kern, torch.Tensor):
+        kern = torch.as_tensor(kern)
+    _check_inputs(xin, kern)
+    check_every, maxit = max(1, int(check_every)), max(0, int(maxit))
+    home = xin.device
+    xin, lmbd, rho, kern = _stage(xin, lmbd, rho, kern)  # once: the chunks below see device tensors
+    x, state, done = None, None, 0
+    while True:
+        n = min(check_every, maxit - done)
+        xn, state = fft_admm_tv_state(xin, lmbd, rho, kern, iso, n, state)
+        done += n
+        if done >= maxit:
+            return xn.to(device=home), state, done
+        diff = xn if x is None else xn - x
+        c = torch.linalg.vector_norm(diff.double()) / torch.linalg.vector_norm(xn.double())
+        x = xn
+        if float(c) <= tol:  # the chunk's one host synchronisation
+            return x.to(device=home), state, done
 
 
 def fft_admm_tv_grouped(xin: torch.Tensor, lmbds, rhos, kern: torch.Tensor, iso: bool = False,

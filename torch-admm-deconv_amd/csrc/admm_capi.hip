@@ -18,6 +18,7 @@
 #include "knobs.hpp"
 #include "mixed_capi.hpp"
 #include "odd_capi.hpp"
+#include "state_kernels.hpp"
 #include "admm_tv.h"
 
 using namespace admm;
@@ -1465,10 +1466,101 @@ template <class T> struct HistView {
 };
 
 
+// ------------------------------------------------------------------ solver state in and out (state_kernels.hpp)
+// A stateful solve (admm_tv_forward_state): where the iterations start (in: null = the reference's zeros) and
+// whether the state after the last one is wanted (out).  One module, no cross-rank hook.
+struct StateIO {
+    const admm_tv_state* in;
+    const admm_tv_state* out;
+};
+
+// pixels per thread of the state kernels: 4 (16-byte accesses) where the row length and every pointer allow
+int state_vec(int W, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    if (W % 4 == 0 && bits % 16 == 0) return 4;
+    if (W % 2 == 0 && bits % 8 == 0) return 2;
+    return 1;
+}
+// block shape: 2^lgtx pixel groups of 256 >> lgtx rows; grid (row blocks, column chunks)
+struct StateGrid {
+    int lgtx;
+    dim3 grid;
+    unsigned rowblocks;
+};
+StateGrid state_grid(long long rows, int W, int V) {
+    const int wv = W / V;
+    int lg = 0;
+    while (lg < 8 && (1 << lg) < wv) ++lg;
+    const int ry = 256 >> lg;
+    const unsigned rb = (unsigned)((rows + ry - 1) / ry);
+    return {lg, dim3(rb, (unsigned)((wv + (1 << lg) - 1) >> lg)), rb};
+}
+int state_rows_check(const admm_tv_desc& d) {
+    if (d.B * d.C * d.H > 0x7fffffffLL)
+        return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_state: more than 2^31 - 1 image rows (B C H)");
+    return 0;
+}
+
+// v = b + rho D^T (z0 - u0) into `v` (pixel order) and u0 into uxo / uyo in the path's layout (L lanes
+// lane-paired, 0: pixel order)
+int state_import(const admm_tv_desc& d, const admm_tv_state& st, const float* b, float* v, float* uxo, float* uyo,
+                 const float* lam, const float* rho, int L, hipStream_t s) {
+    ProfScope ps(3, s);
+    if (int e = state_rows_check(d)) return e;
+    const long long rows = d.B * d.C * d.H;
+    const int W = (int)d.W;
+    const int V = state_vec(W, {st.zx, st.zy, st.ux, st.uy, b, v, uxo, uyo});
+    const StateGrid g = state_grid(rows, W, V);
+    const StateImportArgs a{st.zx, st.zy, st.ux, st.uy, b, v, uxo, uyo, lam, rho, (int)d.H, W, L, g.lgtx, (unsigned)rows};
+    if (V == 4) hipLaunchKernelGGL(k_state_import<4>, g.grid, dim3(256), 0, s, a);
+    else if (V == 2) hipLaunchKernelGGL(k_state_import<2>, g.grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_state_import<1>, g.grid, dim3(256), 0, s, a);
+    return launch_check("k_state_import");
+}
+
+// z_K, u_K into `st` from x_K (pixel order) and u_{K-1} (uxp / uyp in the path's layout; null: zero); iso: the
+// norm over every plane through the layout's part / nsq regions first
+int state_export(const admm_tv_desc& d, const Layout& Lo, void* ws, const float* x, const float* uxp, const float* uyp,
+                 const admm_tv_state& st, const float* lam, const float* rho, int L, hipStream_t s) {
+    if (int e = state_rows_check(d)) return e;
+    const long long P = d.B * d.C, rows = P * d.H;
+    const int H = (int)d.H, W = (int)d.W;
+    float* nsq = d.iso ? at<float>(ws, Lo.nsq) : nullptr;
+    float* part = d.iso ? at<float>(ws, Lo.part) : nullptr;
+    const int V = state_vec(W, {st.zx, st.zy, st.ux, st.uy, x, uxp, uyp});
+    const StateGrid g = state_grid(rows, W, V);
+    StateExportArgs a{x, uxp, uyp, st.zx, st.zy, st.ux, st.uy, nsq, part, lam, rho, H, W, L, g.lgtx, (unsigned)rows, Lo.ppg, P};
+    if (d.iso) {
+        ProfScope ps(2, s);
+        const StateGrid gi = state_grid(H, W, V);
+        const dim3 grid(gi.rowblocks * (unsigned)Lo.ngroups, gi.grid.y);
+        if (V == 4) hipLaunchKernelGGL(k_state_iso_part<4>, grid, dim3(256), 0, s, a, gi.rowblocks);
+        else if (V == 2) hipLaunchKernelGGL(k_state_iso_part<2>, grid, dim3(256), 0, s, a, gi.rowblocks);
+        else hipLaunchKernelGGL(k_state_iso_part<1>, grid, dim3(256), 0, s, a, gi.rowblocks);
+        if (int e = launch_check("k_state_iso_part")) return e;
+        const long long n = 2LL * H * W;
+        hipLaunchKernelGGL(k_state_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, nsq, Lo.ngroups, n);
+        if (int e = launch_check("k_state_reduce")) return e;
+    }
+    ProfScope ps(3, s);
+    if (d.iso) {
+        if (V == 4) hipLaunchKernelGGL((k_state_export<4, true>), g.grid, dim3(256), 0, s, a);
+        else if (V == 2) hipLaunchKernelGGL((k_state_export<2, true>), g.grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_state_export<1, true>), g.grid, dim3(256), 0, s, a);
+    } else {
+        if (V == 4) hipLaunchKernelGGL((k_state_export<4, false>), g.grid, dim3(256), 0, s, a);
+        else if (V == 2) hipLaunchKernelGGL((k_state_export<2, false>), g.grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_state_export<1, false>), g.grid, dim3(256), 0, s, a);
+    }
+    return launch_check("k_state_export");
+}
+
+
 // generic-size forward (same contract as run_forward; generic_kernels.hpp)
 template <class T>
 int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const T* lam, const T* rho, T* out, void* ws,
-                    void* hist, hipStream_t s) {
+                    void* hist, hipStream_t s, const StateIO* sio = nullptr) {
     using C = cx_t<T>;
     const long long P = d.B * d.C;
     const int H = (int)d.H, W = (int)d.W;
@@ -1491,6 +1583,17 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         if (int e = gapply(xin, bb, spec, Lo, ws, d, 1, s)) return e;
         bimg = bb;
     }
+    // a stateful solve (fp32 inference; fused_forward): r_1 from v = b + rho D^T (z0 - u0) in `out`, u0 the
+    // first iteration's u input; the odd-length row pass does not know about state, so such a solve keeps
+    // the three-launch iteration
+    const bool stateful = sio != nullptr, sin = sio && sio->in, sout = sio && sio->out;
+    const T* r1img = bimg;
+    if constexpr (!kF64<T>) {
+        if (sin) {
+            if (int e = state_import(d, *sio->in, bimg, out, u[0], u[1], lam, rho, 0, s)) return e;
+            r1img = out;
+        }
+    }
     // the iteration loop over planes [p0, p0 + np) on stream st (every plane, or -- aniso inference,
     // whose planes are independent -- one half per stream, ADMM_GEN_STREAMS)
     auto solve_planes = [&](long long p0, long long np, hipStream_t st) -> int {
@@ -1505,10 +1608,10 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
     const long long crows = np * H;
     {
         ProfScope ps(3, st);
-        if (int e = grow_fwd(cb, cspec, twW, W, crows, st, gs, ld)) return e;  // r_1 = b
+        if (int e = grow_fwd(r1img + io, cspec, twW, W, crows, st, gs, ld)) return e;  // r_1 = b (or from the state)
     }
     if constexpr (!kF64<T>) {
-        if (Lo.odd && !train) {
+        if (Lo.odd && !train && !stateful) {
             // the two-launch iteration (odd_kernels.hpp): the column pass in place on spec[cur], then pass A
             // (inverse rows, step, forward rows) from spec[cur] into spec[1 - cur]; u ping-pong as below
             C* sp[2] = {cspec, at<C>(ws, Lo.spec2) + so};
@@ -1545,7 +1648,7 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         }
         if (last && !train) break;
         const T* xk = last ? cout : cx;
-        const bool first = it == 1;
+        const bool first = it == 1 && !sin;
         const T *uxi, *uyi, *nprev = nullptr;
         T *uxo, *uyo;
         if (train) {
@@ -1621,9 +1724,18 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         const hipError_t je = fj.finish();
         if (e) return e;
         if (je != hipSuccess) return fail(ADMM_TV_EHIP, std::string("join: ") + hipGetErrorString(je));
-        return 0;
+    } else {
+        if (int e = solve_planes(0, P, s)) return e;
     }
-    return solve_planes(0, P, s);
+    if constexpr (!kF64<T>) {
+        if (sout) {  // after K - 1 steps u_{K-1} is in u[2 ((K-1) & 1)] (the imported u0, or none, when K = 1)
+            const int ui = (d.maxit - 1) & 1;
+            const bool none = d.maxit == 1 && !sin;
+            return state_export(d, Lo, ws, out, none ? nullptr : u[2 * ui], none ? nullptr : u[2 * ui + 1], *sio->out, lam,
+                                rho, 0, s);
+        }
+    }
+    return 0;
 }
 
 // rows per strip of the mixed row pass: the R dividing H that minimises (rounds of blocks over the chip)
@@ -1705,6 +1817,12 @@ struct Pow2Ops : FusedOps {
     // rows of 1,024+ where the pixel-order streams measured faster (C3 pass A 1.0355 -> 1.0295 ms, 4
     // interleaved rounds, profiles/r03_sweep_knobs_c3.txt).
     bool lane_paired(bool train) const { return !train && env_int("ADMM_PL", (d.iso || d.W < 1024) ? 1 : 0) != 0; }
+    // lanes per row of the lane-paired layout (the state kernels address u and b through it)
+    int row_lanes() const {
+        int L = 0;
+        with_row(N, [&](auto ops) { return L = decltype(ops)::G::L; });
+        return L;
+    }
     int strip(long long rows, bool aniso_fwd) const { return strip_rows(H, N, rows, aniso_fwd, coop && !rev); }
     int r2c(const float* img, cf* spec, long long rows, hipStream_t s, bool pl = false) const {
         return with_row(N, [&](auto ops) { return decltype(ops)::r2c(img, spec, twW, rows, s, pl); });
@@ -1754,6 +1872,7 @@ struct MixedOps : FusedOps {
     // with its own Wiener factor, lambda, rho and (iso) norm, sharing b, the tables and the regions
     int modules_per_pass(int) const { return 1; }
     bool lane_paired(bool) const { return false; }  // pixel order throughout
+    int row_lanes() const { return 0; }
     int strip(long long rows, bool) const { return strip_rows_mixed(H, rows, N); }
     int r2c(const float* img, cf* spec, long long rows, hipStream_t s, bool = false) const {
         return hip_code(admm_mixed::r2c(N, img, spec, twW, rows, s), "k_row_r2c_m");
@@ -1814,11 +1933,15 @@ struct MixedOps : FusedOps {
 // y image at 2(k-1)+1), N_k -> norm slot k-1, and the last iteration's row pass also runs (a_K is needed
 // by the backward); with a PSF gradient (Hist::keep_t) every r_k's row spectra are kept too, so r_1 goes
 // to the history, the column pass reads r_k from there and the row pass writes r_{k+1} there.
+// sio (inference, one module): a stateful solve.  With sio->in, r_1 is the row transform of v = b + rho D^T (z0 -
+// u0), which the import kernel leaves in `out`, u0 is the first iteration's u input and that iteration runs
+// the steady kernels; with sio->out the row pass of iteration K - 1 keeps its u stores and the export kernel
+// follows the output transform.  sio == nullptr launches exactly what it always did.
 // (measured and removed: plane chunks kept resident in the Infinity Cache through all iterations, and
 // two plane halves on two streams -- DESIGN.md §9; both no faster at C3)
 template <class B>
 int fused_forward(const B& be, const float* xin, const float* lam, const float* rho, float* out, void* hist,
-                  hipStream_t s) {
+                  hipStream_t s, const StateIO* sio = nullptr) {
     const admm_tv_desc& d = be.d;
     const Layout& Lo = be.Lo;
     void* ws = be.ws;
@@ -1841,6 +1964,8 @@ int fused_forward(const B& be, const float* xin, const float* lam, const float* 
     const long long np = ng * Pm, rows = np * H;  // planes and rows of a pass
     const int gpm = Lo.ngroups / G;               // iso plane groups per module (a group never straddles two)
     const int R = be.strip(rows, !d.iso && !train);
+    const bool sin = sio && sio->in, sout = sio && sio->out;
+    const int sl = pl ? be.row_lanes() : 0;  // the state kernels' view of the u / b layout
     for (int g0 = 0; g0 < G; g0 += ng) {
         const float* lamg = lam + g0;
         const float* rhog = rho + g0;
@@ -1848,6 +1973,11 @@ int fused_forward(const B& be, const float* xin, const float* lam, const float* 
         for (int g = 0; g < ng; ++g) {  // r_1 = b for every module of the pass (the one before overwrote it)
             ProfScope ps(3, s);
             cf* t0 = (keep_t ? hv.r(1) : spec[0]) + (size_t)g * Pm * H * N;
+            if (sin) {  // r_1 from the state: v in `out` (free until the output transform), u0 into u[0], u[1]
+                if (int e = state_import(d, *sio->in, bimg, outg, u[0], u[1], lamg, rhog, sl, s)) return e;
+                if (int e = be.r2c(outg, t0, Pm * H, s, false)) return e;
+                continue;
+            }
             if (int e = be.r2c(bimg, t0, Pm * H, s, pl)) return e;
         }
         int cur = 0, uin = 0;  // spec[cur] holds the current r spectra; u[2*uin], u[2*uin+1] = u_x, u_y in
@@ -1859,9 +1989,15 @@ int fused_forward(const B& be, const float* xin, const float* lam, const float* 
             if (it == d.maxit) {
                 ProfScope ps(3, s);
                 if (int e = be.c2r(spec[cur], outg, rows, s)) return e;
+                if (sout) {  // u[2 uin], u[2 uin + 1]: u_{K-1} -- iteration K - 1's, the imported u0, or none
+                    const bool none = d.maxit == 1 && !sin;
+                    if (int e = state_export(d, Lo, ws, outg, none ? nullptr : u[2 * uin], none ? nullptr : u[2 * uin + 1],
+                                             *sio->out, lamg, rhog, sl, s))
+                        return e;
+                }
                 if (!train) break;
             }
-            const bool first = (it == 1);
+            const bool first = (it == 1) && !sin;
             const float *uxi, *uyi, *nprev = nullptr;
             float *uxo, *uyo;
             if (train) {  // a_{k-1} in, a_k out (u is rebuilt from a in the kernels)
@@ -1877,7 +2013,8 @@ int fused_forward(const B& be, const float* xin, const float* lam, const float* 
                 uyo = u[2 * (1 - uin) + 1];
                 // the last row pass of the solve: only its r spectra are used (the last column pass and
                 // the output transform follow), so it writes no u (k_pass_a: a null output)
-                if (it == d.maxit - 1) uxo = uyo = nullptr;
+                // (kept when the state is wanted: the export forms a_K from this u)
+                if (it == d.maxit - 1 && !sout) uxo = uyo = nullptr;
             }
             const float* nsq = nullptr;
             if (d.iso) {
@@ -1959,6 +2096,43 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
     if (Lo.mixed && (!hist || Lo.mixed_train)) return fused_forward(MixedOps(d, Lo, ws), xin, lam, rho, out, hist, s);
     if (Lo.gen) return run_forward_gen(d, Lo, xin, lam, rho, out, ws, hist, s);
     return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, hist, s);
+}
+
+// what a stateful solve refuses (admm_tv_forward_state, admm_tv_state_workspace_size, admm_tv_path(desc, 2))
+int state_check(const admm_tv_desc& d) {
+    if (d.flags & (ADMM_TV_FLAG_F64 | ADMM_TV_FLAG_PSF_GRAD))
+        return fail(ADMM_TV_EINVAL, "admm_tv_forward_state: fp32 inference only (ADMM_TV_FLAG_F64 / ADMM_TV_FLAG_PSF_GRAD set)");
+    if (d.groups > 1) return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_state: groups > 1 (one stateful solve per module)");
+    if (d.allreduce) return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_state: no cross-rank all-reduce hook");
+    // the state kernels run one block row per image row (as the generic step kernel does): B C H < 2^31.  Checked
+    // here, so that the size and path queries answer as the call does.
+    return state_rows_check(d);
+}
+
+// The stateful forward solver (admm_tv_forward_state's contract, its descriptor already validated): the
+// iterations of run_forward's inference solve, started from st.in and followed by the export of st.out.
+int run_forward_state(const admm_tv_desc& d, const float* xin, const float* kern, const float* lam, const float* rho,
+                      const StateIO& st, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
+    const Layout Lo = make_layout(d);
+    if (int e = check_workspace(ws, ws_bytes, Lo.total)) return e;
+    const size_t img_bytes = (size_t)d.B * d.C * d.H * d.W * sizeof(float);
+    if (d.maxit == 0) {  // x = zeros (deconv.py:61,117); the state passes through
+        if (img_bytes) HIPCHK(hipMemsetAsync(out, 0, img_bytes, s));
+        if (st.out && img_bytes) {
+            float* const dst[4] = {st.out->zx, st.out->zy, st.out->ux, st.out->uy};
+            const float* const src[4] = {st.in ? st.in->zx : nullptr, st.in ? st.in->zy : nullptr,
+                                         st.in ? st.in->ux : nullptr, st.in ? st.in->uy : nullptr};
+            for (int i = 0; i < 4; ++i) {
+                if (!st.in) HIPCHK(hipMemsetAsync(dst[i], 0, img_bytes, s));
+                else if (dst[i] != src[i]) HIPCHK(hipMemcpyAsync(dst[i], src[i], img_bytes, hipMemcpyDeviceToDevice, s));
+            }
+        }
+        return 0;
+    }
+    if (int e = setup(d, Lo, ws, kern, rho, s)) return e;
+    if (Lo.mixed) return fused_forward(MixedOps(d, Lo, ws), xin, lam, rho, out, nullptr, s, &st);
+    if (Lo.gen) return run_forward_gen<float>(d, Lo, xin, lam, rho, out, ws, nullptr, s, &st);
+    return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, nullptr, s, &st);
 }
 
 // backward workspace = forward layout + a^ ping-pong (4 images) + b^ + per-iteration partials
@@ -2333,6 +2507,12 @@ int admm_tv_supported_f64(int64_t H, int64_t W) { return f64_hw(H, W) ? 1 : 0; }
 
 int admm_tv_path(const admm_tv_desc* d, int train) {
     if (int e = validate(d)) return e;
+    if (train == 2) {  // admm_tv_forward_state: the fused paths, else the generic loop (also where the plain
+                       // solve takes the odd-length row pass, which carries no state)
+        if (int e = state_check(*d)) return e;
+        const Layout Lo = make_layout(*d);
+        return !Lo.gen ? ADMM_TV_PATH_FUSED : Lo.mixed ? ADMM_TV_PATH_MIXED : ADMM_TV_PATH_GENERIC;
+    }
     if (train) {
         if (int e = grouped_train_check(*d)) return e;
     }
@@ -2363,6 +2543,29 @@ int admm_tv_forward(const admm_tv_desc* dp, const float* xin, const float* kern,
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
     if (int e = dg.check()) return e;
     return run_forward(*dp, xin, kern, lam, rho, out, ws, ws_bytes, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int admm_tv_state_workspace_size(const admm_tv_desc* d, size_t* bytes) {
+    if (int e = validate(d)) return e;
+    if (int e = state_check(*d)) return e;
+    if (!bytes) return fail(ADMM_TV_EINVAL, "null bytes");
+    *bytes = make_layout(*d).total;  // the forward's regions serve: v lives in `out`, the iso norm in part / nsq
+    return 0;
+}
+
+int admm_tv_forward_state(const admm_tv_desc* dp, const float* xin, const float* kern, const float* lam,
+                          const float* rho, const admm_tv_state* state_in, const admm_tv_state* state_out, float* out,
+                          void* ws, size_t ws_bytes, void* stream) {
+    if (int e = validate(dp)) return e;
+    if (int e = state_check(*dp)) return e;
+    if (!xin || !out || !lam || !rho || (dp->kh > 0 && !kern)) return fail(ADMM_TV_EINVAL, "null pointer argument");
+    for (const admm_tv_state* st : {state_in, state_out})
+        if (st && (!st->zx || !st->zy || !st->ux || !st->uy))
+            return fail(ADMM_TV_EINVAL, "admm_tv_state with a null member (pass a NULL struct for no state)");
+    DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
+    if (int e = dg.check()) return e;
+    return run_forward_state(*dp, xin, kern, lam, rho, StateIO{state_in, state_out}, out, ws, ws_bytes,
+                             reinterpret_cast<hipStream_t>(stream));
 }
 
 int admm_tv_history_size(const admm_tv_desc* d, size_t* bytes) {
