@@ -94,6 +94,29 @@ typedef struct admm_tv_desc {
  * return the fp64 sizes.  fp64 solves run on the generic (any-size) kernels' double instantiation at
  * every H, W that admm_tv_supported_f64 accepts; groups must be 0 or 1. */
 #define ADMM_TV_FLAG_F64 2
+/* flags: a PSF bank -- a PSF per image, per channel or per plane instead of one for all B*C planes (a batch
+ * of images each with its own measured blur; optics whose PSF differs between R, G and B).  kern is then a
+ * contiguous (Bk, Ck, kh, kw) fp32 device array, Bk = B with ADMM_TV_FLAG_PSF_PER_IMAGE (else 1), Ck = C with
+ * ADMM_TV_FLAG_PSF_PER_CHANNEL (else 1); plane (b, c) uses PSF t = (Bk > 1 ? b : 0) * Ck + (Ck > 1 ? c : 0).
+ * All PSFs of a bank share kh = kw (zero-pad smaller ones); rho and lambda are shared by the bank, and the
+ * iso norm still runs over every (b, c) plane, which a loop of single-image calls would lose.  With neither
+ * bit set everything is as without them.
+ *  - Honoured by admm_tv_workspace_size, admm_tv_state_workspace_size, admm_tv_forward,
+ *    admm_tv_forward_state, admm_tv_psf_transpose (b of plane (b, c) is H_t with PSF t) and admm_tv_path
+ *    (modes 0 and 2).  The workspace holds T = Bk * Ck copies of the PSF tables (the Wiener factor and its
+ *    packed copy, the H_t multiplier, the PSF row spectra): about 8 bytes per half-spectrum point and table
+ *    at power-of-two sizes.
+ *  - Paths: the fused power-of-two and smooth-size iterations where admm_tv_forward takes them, the generic
+ *    three-launch iteration everywhere else -- the odd row lengths (admm_tv_supported == 4, either
+ *    orientation) included, as for stateful solves; admm_tv_path reports ADMM_TV_PATH_GENERIC there.
+ *  - Refused, by the size queries and admm_tv_path as by the calls: kh == 0 (ADMM_TV_EINVAL); groups > 1, an
+ *    all-reduce hook, ADMM_TV_FLAG_F64 (every *_f64 entry point), ADMM_TV_FLAG_PSF_GRAD, more than 65,535
+ *    PSFs, and the training entry points (admm_tv_forward_train, admm_tv_backward, admm_tv_history_size,
+ *    admm_tv_backward_workspace_size): ADMM_TV_EUNSUPPORTED.  Training with a bank is the next step and is
+ *    not implemented: a bank is inference only. */
+#define ADMM_TV_FLAG_PSF_PER_IMAGE 4   /* kern holds B  PSFs: image b uses PSF b            */
+#define ADMM_TV_FLAG_PSF_PER_CHANNEL 8 /* kern holds C  PSFs: channel c uses PSF c          */
+/* both: kern holds B*C PSFs, plane (b, c) uses PSF b*C + c                                  */
 
 /* ABI version (ADMM_TV_ABI_VERSION). */
 int admm_tv_abi_version(void);

@@ -94,6 +94,9 @@ class AdmmTvState(ctypes.Structure):
 
 ADMM_TV_FLAG_PSF_GRAD = 1
 ADMM_TV_FLAG_F64 = 2  # fp64 solve: the *_f64 entry points, double arrays
+# a PSF bank: kern holds (Bk, Ck, k, k) PSFs, plane (b, c) uses PSF (Bk > 1 ? b : 0) * Ck + (Ck > 1 ? c : 0)
+ADMM_TV_FLAG_PSF_PER_IMAGE = 4    # Bk = B
+ADMM_TV_FLAG_PSF_PER_CHANNEL = 8  # Ck = C
 ABI_VERSION = 7
 # admm_tv_path codes (include/admm_tv.h)
 PATHS = {1: "fused", 2: "generic", 3: "fused mixed-radix", 4: "fused odd-length"}
@@ -301,7 +304,20 @@ def path(d: AdmmTvDesc, train: bool = False, mode: int = None) -> str:
     code = load().admm_tv_path(ctypes.byref(d), int(mode) if mode is not None else (1 if train else 0))
     if code < 0:
         check(code)
+    if code not in PATHS:
+        raise NativeError(code, "admm_tv_path returned a path code this binding does not know")
     return PATHS[code]
+
+
+def bank_flags(kern_shape, B: int, C: int) -> int:
+    """The PSF-bank bits of a (Bk, Ck, k, k) kern for a (B, C, H, W) input: Bk in {1, B}, Ck in {1, C}
+    (ValueError otherwise).  A (1, 1, k, k) kern sets none; neither does a leading size that is 1 because B or
+    C is (the one PSF serves every plane either way)."""
+    if len(kern_shape) != 4 or kern_shape[0] not in (1, B) or kern_shape[1] not in (1, C):
+        raise ValueError(f"PSF bank of shape {tuple(kern_shape)}: expected (Bk, Ck, k, k) with Bk in (1, {B}) and "
+                         f"Ck in (1, {C})")
+    return ((ADMM_TV_FLAG_PSF_PER_IMAGE if kern_shape[0] > 1 else 0)
+            | (ADMM_TV_FLAG_PSF_PER_CHANNEL if kern_shape[1] > 1 else 0))
 
 
 def supported(H: int, W: int, f64: bool = False) -> bool:

@@ -6,7 +6,9 @@ it is registered as custom operators with fake (meta) kernels: tracing keeps it 
 graph, with no graph break, and the autograd formula is registered on the op itself.
 
   admm_hip::fft_admm_tv_fwd(x, lam, rho, kern, iso, maxit) -> out
-      inference solve (admm_tv_forward); out has G*B planes for G = lam.numel() modules
+      inference solve (admm_tv_forward); out has G*B planes for G = lam.numel() modules.  kern is
+      (1, 1, k, k), empty, or a PSF bank (Bk, Ck, k, k) with Bk in {1, B}, Ck in {1, C} (one module; the
+      stateful op takes one too, the training op refuses it)
   admm_hip::fft_admm_tv_state(x, lam, rho, kern, state, iso, maxit) -> (out, z_x, z_y, u_x, u_y)
       the stateful inference solve (admm_tv_forward_state): iterations from `state` (the reference's
       z_x, z_y, u_x, u_y, or an empty list for zeros), the state afterwards as new tensors
@@ -61,6 +63,14 @@ def _flags(kern: Tensor, psf_grad: bool) -> int:
     return _native.ADMM_TV_FLAG_PSF_GRAD if (psf_grad and kern.numel() > 0) else 0
 
 
+def _bank(x: Tensor, kern: Tensor) -> int:
+    """The PSF-bank flag bits of kern's leading dimensions: (Bk, Ck, k, k) with Bk in {1, B}, Ck in {1, C}
+    (anything else: ValueError); none for a (1, 1, k, k) or an empty kern."""
+    if kern.numel() == 0:
+        return 0
+    return _native.bank_flags(kern.shape, int(x.shape[0]), int(x.shape[1]))
+
+
 def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
@@ -78,7 +88,7 @@ def fft_admm_tv_fwd(x: Tensor, lam: Tensor, rho: Tensor, kern: Tensor, iso: bool
     _check_device(x, lam, rho, kern)
     B, C, H, W = x.shape
     _check_supported(H, W, _f64(x))
-    d = _desc(x, lam, kern, iso, maxit)
+    d = _desc(x, lam, kern, iso, maxit, _bank(x, kern))  # a (Bk, Ck, k, k) kern: a PSF bank
     x, lam, rho, kern = x.contiguous(), lam.contiguous(), rho.contiguous(), kern.contiguous()
     ws = torch.empty(_native.workspace_size(d), dtype=torch.uint8, device=x.device)
     out = torch.empty((lam.numel() * B, C, H, W), dtype=x.dtype, device=x.device)
@@ -107,7 +117,7 @@ def fft_admm_tv_state(x: Tensor, lam: Tensor, rho: Tensor, kern: Tensor, state: 
         raise ValueError("admm_hip::fft_admm_tv_state: state is (z_x, z_y, u_x, u_y) or empty")
     B, C, H, W = x.shape
     _check_supported(H, W, False)
-    d = _desc(x, lam, kern, iso, maxit)
+    d = _desc(x, lam, kern, iso, maxit, _bank(x, kern))  # a (Bk, Ck, k, k) kern: a PSF bank
     x, lam, rho, kern = x.contiguous(), lam.contiguous(), rho.contiguous(), kern.contiguous()
     sin = [t.contiguous() for t in state]
     for t in sin:
@@ -139,6 +149,9 @@ def fft_admm_tv_fwd_train(x: Tensor, lam: Tensor, rho: Tensor, kern: Tensor, iso
                           psf_grad: bool) -> Tuple[Tensor, Tensor]:
     """admm_tv_forward_train: the solve plus the history its backward reads (a_k per iteration,
     iso norms, and with psf_grad the r_k spectra)."""
+    if _bank(x, kern):
+        raise NotImplementedError("admm_hip::fft_admm_tv_fwd_train: a PSF bank is inference only (training with "
+                                  "a bank is not implemented)")
     _check_device(x, lam, rho, kern)
     B, C, H, W = x.shape
     _check_supported(H, W, _f64(x))

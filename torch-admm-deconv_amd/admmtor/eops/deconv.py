@@ -37,6 +37,8 @@ __all__ = [
     "ADMMState",
     "fft_admm_tv_state",
     "fft_admm_tv_until",
+    "fft_admm_tv_bank",
+    "fft_admm_tv_bank_state",
 ]
 
 
@@ -300,6 +302,99 @@ def fft_admm_tv_state(xin: torch.Tensor, lmbd, rho, kern: torch.Tensor, iso: boo
         out, zx, zy, ux, uy = torch.ops.admm_hip.fft_admm_tv_state(
             xc, _as_device_scalar(lmbd, dev), _as_device_scalar(rho, dev), kc, sin, bool(iso), maxit)
     return out.to(device=home), ADMMState(zx, zy, ux, uy)
+
+
+def _check_bank(xin: torch.Tensor, kerns: torch.Tensor, who: str) -> None:
+    """Validation of the PSF-bank calls, on host tensors too (nothing here needs a device)."""
+    if not isinstance(xin, torch.Tensor):
+        raise TypeError("xin must be a torch.Tensor")
+    if xin.dim() != 4:
+        raise ValueError(f"{who} expects a 4-D (B, C, H, W) input, got shape {tuple(xin.shape)}")
+    if not isinstance(kerns, torch.Tensor):
+        raise TypeError("kerns must be a torch.Tensor of shape (Bk, Ck, k, k)")
+    if kerns.numel() == 0:
+        raise ValueError(f"{who}: an empty PSF bank; fft_admm_tv is the call for a solve without a PSF")
+    autocast = xin.is_cuda and torch.is_autocast_enabled("cuda")
+    if xin.dtype in (torch.float16, torch.bfloat16) and not autocast:
+        raise RuntimeError(f"Unsupported dtype {xin.dtype}")
+    _native.bank_flags(kerns.shape, int(xin.shape[0]), int(xin.shape[1]))  # ValueError for any other leading shape
+    if kerns.shape[2] != kerns.shape[3]:
+        raise RuntimeError(f"non-square PSFs: a bank holds (Bk, Ck, k, k), got {tuple(kerns.shape)}")
+    if not autocast and kerns.dtype != xin.dtype:
+        raise RuntimeError(f"expected kerns dtype {xin.dtype}, got {kerns.dtype}")
+    if xin.dtype == torch.float64:
+        raise NotImplementedError(f"{who}: fp32 solves only (a PSF bank has no fp64 kernels)")
+
+
+def fft_admm_tv_bank_state(xin: torch.Tensor, lmbd, rho, kerns: torch.Tensor, iso: bool = False, maxit: int = 100,
+                           state: Optional[ADMMState] = None) -> Tuple[torch.Tensor, ADMMState]:
+    """:func:`fft_admm_tv_state` with a PSF per image, per channel or per plane: ``(x, state)``.
+
+    ``kerns`` is a bank ``(Bk, Ck, k, k)`` with ``Bk`` in ``{1, B}`` and ``Ck`` in ``{1, C}``: plane ``(b, c)``
+    of ``xin`` is deconvolved with ``kerns[b if Bk > 1 else 0, c if Ck > 1 else 0]`` -- a batch whose images
+    each have their own measured blur, a motion kernel per video frame, optics whose PSF differs between R, G
+    and B.  All PSFs share ``k`` (zero-pad smaller ones around their centre); ``lmbd`` and ``rho`` are shared.
+    One native solve over all ``B C`` planes: the launches of a shared-PSF solve, and for ``iso=True`` the
+    reference's norm over batch and channel, which a loop of single-image calls would not compute.  A
+    ``(1, 1, k, k)`` bank is :func:`fft_admm_tv_state` bit for bit.  The bank may change between calls, like
+    every other input.
+
+    Conventions as :func:`fft_admm_tv_state`: inference only (``RuntimeError`` if gradients are enabled and an
+    input requires grad), fp32 only (fp64 raises ``NotImplementedError``), host inputs are staged to the
+    current ROCm device, half inputs under autocast compute in fp32.  ``ValueError`` for any other leading
+    shape of ``kerns`` and for an empty bank, ``RuntimeError`` for ``kh != kw`` or a dtype mismatch.
+    """
+    if not isinstance(kerns, torch.Tensor):
+        kerns = torch.as_tensor(kerns)
+    _check_bank(xin, kerns, "fft_admm_tv_bank_state")
+    if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad
+                                       for v in (xin, lmbd, rho, kerns, *(state or ()))):
+        raise RuntimeError("a PSF bank is inference only: an input requires grad (training with a bank is not "
+                           "implemented; run under torch.no_grad())")
+    home = xin.device
+    maxit = max(0, int(maxit))
+    xin, lmbd, rho, kerns = _stage(xin, lmbd, rho, kerns)
+    dev = xin.device
+    if state is not None:
+        if len(state) != 4:
+            raise ValueError("state must be ADMMState(z_x, z_y, u_x, u_y)")
+        for name, t in zip(ADMMState._fields, state):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(xin.shape) or t.dtype != torch.float32 \
+                    or t.device != dev:
+                raise ValueError(f"state.{name} must be an fp32 tensor of shape {tuple(xin.shape)} on {dev}")
+    with torch.no_grad():
+        xc = xin.detach().to(torch.float32).contiguous()
+        kc = kerns.detach().to(device=dev, dtype=torch.float32).contiguous()
+        sin = [t.detach().contiguous() for t in state] if state is not None else []
+        out, zx, zy, ux, uy = torch.ops.admm_hip.fft_admm_tv_state(
+            xc, _as_device_scalar(lmbd, dev), _as_device_scalar(rho, dev), kc, sin, bool(iso), maxit)
+    return out.to(device=home), ADMMState(zx, zy, ux, uy)
+
+
+def fft_admm_tv_bank(xin: torch.Tensor, lmbd, rho, kerns: torch.Tensor, iso: bool = False,
+                     maxit: int = 100) -> torch.Tensor:
+    """:func:`fft_admm_tv` with a PSF per image, per channel or per plane (``kerns`` of shape
+    ``(Bk, Ck, k, k)``, see :func:`fft_admm_tv_bank_state`, whose conventions and errors apply): the last x,
+    on ``xin``'s device.  A ``(1, 1, k, k)`` bank gives :func:`fft_admm_tv`'s result bit for bit."""
+    if not isinstance(kerns, torch.Tensor):
+        kerns = torch.as_tensor(kerns)
+    _check_bank(xin, kerns, "fft_admm_tv_bank")
+    if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad
+                                       for v in (xin, lmbd, rho, kerns)):
+        raise RuntimeError("a PSF bank is inference only: an input requires grad (training with a bank is not "
+                           "implemented; run under torch.no_grad())")
+    home = xin.device
+    maxit = max(0, int(maxit))
+    if xin.numel() == 0:
+        return torch.zeros(xin.shape, dtype=torch.float32, device=home)
+    xin, lmbd, rho, kerns = _stage(xin, lmbd, rho, kerns)
+    dev = xin.device
+    with torch.no_grad():
+        xc = xin.detach().to(torch.float32).contiguous()
+        kc = kerns.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out = torch.ops.admm_hip.fft_admm_tv_fwd(xc, _as_device_scalar(lmbd, dev), _as_device_scalar(rho, dev), kc,
+                                                 bool(iso), maxit)
+    return out.to(device=home)
 
 
 def fft_admm_tv_until(xin: torch.Tensor, lmbd, rho, kern: torch.Tensor, iso: bool = False, tol: float = 1e-4,

@@ -154,6 +154,18 @@ MMPlan mm_plan_row(int W);  // the row inverse (k_grow_inv_mm): W = S R, S in {1
 // modules solved together (admm_tv_desc.groups)
 int ngroups_of(const admm_tv_desc& d) { return d.groups > 1 ? d.groups : 1; }
 
+// a PSF bank (ADMM_TV_FLAG_PSF_PER_IMAGE / _PER_CHANNEL): kern holds (Bk, Ck, k, k) PSFs and the solve T = Bk Ck
+// copies of every PSF table; plane p = b C + c takes table (Bk > 1 ? b : 0) Ck + (Ck > 1 ? c : 0)
+bool is_bank(const admm_tv_desc& d) { return (d.flags & (ADMM_TV_FLAG_PSF_PER_IMAGE | ADMM_TV_FLAG_PSF_PER_CHANNEL)) != 0; }
+BankIdx bank_of(const admm_tv_desc& d) {
+    const int Bk = (d.flags & ADMM_TV_FLAG_PSF_PER_IMAGE) ? (int)d.B : 1;
+    const int Ck = (d.flags & ADMM_TV_FLAG_PSF_PER_CHANNEL) ? (int)d.C : 1;
+    return BankIdx{(int)d.C, Bk > 1 ? Ck : 0, Ck > 1 ? 1 : 0, Bk * Ck};
+}
+// planes in a row that share a table (the column pass's planes per block divide it)
+int bank_run(const admm_tv_desc& d) { return (d.flags & ADMM_TV_FLAG_PSF_PER_CHANNEL) ? 1 : (int)d.C; }
+constexpr long long kBankMax = 65535;  // the setup kernels take the table from a grid dimension
+
 constexpr size_t kAlign = 256;
 size_t up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
@@ -185,6 +197,7 @@ struct Layout {
     int ldw;
 };
 
+// (transposes a single PSF's shape: never reached with a PSF bank, make_layout leaves Layout::tr unset for one)
 admm_tv_desc transposed(const admm_tv_desc& d) {
     admm_tv_desc t = d;
     t.H = d.W;
@@ -209,6 +222,9 @@ Layout make_layout(const admm_tv_desc& d) {
     const size_t img = P * H * W * rs;
     const size_t img_m = (size_t)d.B * d.C * H * W * rs;         // one module's planes
     const int k = d.kh;
+    // a PSF bank: T copies of the PSF tables (G, fcT and its copy, mT; fcM, mM); one module, fp32 (bank_check)
+    const bool bank = is_bank(d);
+    const size_t T = bank ? (size_t)bank_of(d).T : 1;
     size_t o = 0;
     auto take = [&](size_t bytes) {
         size_t at = o;
@@ -217,12 +233,13 @@ Layout make_layout(const admm_tv_desc& d) {
     };
     L.gen = f64 || generic_hw(d.H, d.W);
     if (L.gen && !f64) {
-        L.mm = mm_plan((int)H, (int)W);
+        // (a bank keeps the LDS column pass: the matrix-core one reads one transposed factor table)
+        if (!bank) L.mm = mm_plan((int)H, (int)W);
         L.mmr = mm_plan_row((int)W);
     }
     L.mixed = L.gen && !f64 && mixed_hw(d.H, d.W) && (G == 1 || !(d.flags & ADMM_TV_FLAG_PSF_GRAD));
     L.mixed_train = mixed_train_hw(d);
-    L.odd = L.gen && !f64 && G == 1 && !d.iso && odd_hw(d.H, d.W);
+    L.odd = L.gen && !f64 && G == 1 && !d.iso && !bank && odd_hw(d.H, d.W);  // (the row pass's wrapper knows one PSF)
     L.ldw = (int)(N + 1);
     if (L.gen && !f64 && L.mm.ok && L.mmr.ok && env_int("ADMM_GEN_PITCH", 1)) L.ldw = (int)((N + 1 + 15) / 16 * 16);
     L.spec[0] = take(L.gen ? P * H * (size_t)L.ldw * csz : img);
@@ -236,16 +253,16 @@ Layout make_layout(const admm_tv_desc& d) {
     // one Wiener factor per module (its rho); on the fused path followed by their packed copies for
     // the column pass (k_fc_pack)
     // (generic path: a [H][Wh] copy for the matrix-core column pass, k_fc_transpose)
-    L.fcT = take(G * (N + 1) * H * rs * ((!L.gen || L.mm.ok) ? 2 : 1));
-    L.mT = take((N + 1) * H * csz);
+    L.fcT = take(G * T * (N + 1) * H * rs * ((!L.gen || L.mm.ok) ? 2 : 1));
+    L.mT = take(T * (N + 1) * H * csz);
     // twiddles; on the generic path followed by the plan's Bluestein tables (make_plan)
     L.twW = take((W + (L.gen ? make_plan((int)W, f64).ntab : 0)) * csz);
     L.twH = take((H + (L.gen ? make_plan((int)H, f64).ntab : 0)) * csz);
     L.twHd = take(H * sizeof(double2));
-    L.G = take((size_t)(k > 0 ? k : 1) * (N + 1) * sizeof(double2));
+    L.G = take(T * (size_t)(k > 0 ? k : 1) * (N + 1) * sizeof(double2));
     L.gscr = L.gen ? take(glb_scratch((int)H, (int)W, (long long)P, f64)) : 0;
-    L.fcM = L.mixed ? take(G * (2 * N + 1) * H * sizeof(float)) : 0;  // per module: [H][N + 1] + packed copy, k_fc_mixed
-    L.mM = (L.mixed && k > 0) ? take((N + 1) * H * 2 * sizeof(float)) : 0;
+    L.fcM = L.mixed ? take(G * T * (2 * N + 1) * H * sizeof(float)) : 0;  // per module: [H][N + 1] + packed copy, k_fc_mixed
+    L.mM = (L.mixed && k > 0) ? take(T * (N + 1) * H * 2 * sizeof(float)) : 0;
     L.spec2 = L.odd ? take(P * H * (size_t)L.ldw * csz) : 0;
     L.sigma = (k > 0 && (d.flags & ADMM_TV_FLAG_PSF_GRAD)) ? take((N + 1) * H * sizeof(double2)) : 0;
     if (d.iso) {
@@ -271,7 +288,7 @@ Layout make_layout(const admm_tv_desc& d) {
         L.nsq = take(G * 2 * H * W * rs);  // per module
     }
     L.total = o;
-    if (!f64 && G == 1 && !d.iso && odd_t_hw(d.H, d.W)) {
+    if (!f64 && G == 1 && !d.iso && !bank && odd_t_hw(d.H, d.W)) {
         // the transposed inference solve: [xin^T][result^T][PSF^T][the W x H problem's workspace], laid over
         // the regions above (a call uses one or the other: training and the helpers keep this layout)
         size_t t = 0;
@@ -511,8 +528,10 @@ int passb_gp(int H, int P, int ppm) {
     return g;
 }
 
+// bank: a PSF bank's table index (k_pass_b<H, C, MODE, BankIdx>; ppm is then the run of planes that share a table, which gp
+// divides: 1 for per-channel and per-plane banks, C for per-image ones), null for the shared PSF
 template <int H, int C> int pass_b_hc(const cf* spec, cf* out, const float* fcT, const cf* mT, const cf* twH, int N,
-                                      int P, int mode, int ppm, hipStream_t s) {
+                                      int P, int mode, int ppm, hipStream_t s, const BankIdx* bank) {
     using G = ColGeom<H, C>;
     const int colblocks = N / C;
     const int gp = passb_gp(H, P, ppm);
@@ -525,6 +544,20 @@ template <int H, int C> int pass_b_hc(const cf* spec, cf* out, const float* fcT,
     // 5,624, C3 iso +0.5 %; profiles/r03_sweep_knobs_c3.txt); pair-interleaved remap (4, 5) +9 %
     // (profiles/r03_ab_passb_order.txt)
     const int pmode = env_int("ADMM_PASSB_PMODE", 2);
+    if (bank) {  // inference (mode 0) and H_t (mode 1)
+        if (mode == 0) {
+            if (int e = set_lds(k_pass_b<H, C, 0, BankIdx>, G::lds_bytes())) return e;
+            hipLaunchKernelGGL((k_pass_b<H, C, 0, BankIdx>), grid, dim3(G::NT), G::lds_bytes(), s, spec, out, fcT, mT, twH, N,
+                               colblocks, ppm, order, fpack, gp, P, pmode, *bank);
+        } else if (mode == 1) {
+            if (int e = set_lds(k_pass_b<H, C, 1, BankIdx>, G::lds_bytes())) return e;
+            hipLaunchKernelGGL((k_pass_b<H, C, 1, BankIdx>), grid, dim3(G::NT), G::lds_bytes(), s, spec, out, fcT, mT, twH, N,
+                               colblocks, ppm, order, fpack, gp, P, pmode, *bank);
+        } else {
+            return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: no adjoint column pass (inference only)");
+        }
+        return launch_check("k_pass_b<bank>");
+    }
     if (mode == 0) {
         if (int e = set_lds(k_pass_b<H, C, 0>, G::lds_bytes())) return e;
         hipLaunchKernelGGL((k_pass_b<H, C, 0>), grid, dim3(G::NT), G::lds_bytes(), s, spec, out, fcT, mT, twH, N, colblocks, ppm,
@@ -542,7 +575,7 @@ template <int H, int C> int pass_b_hc(const cf* spec, cf* out, const float* fcT,
 }
 
 template <int H> int pass_b_h(const cf* spec, cf* out, const float* fcT, const cf* mT, const cf* twH, int N, int P,
-                              int mode, int ppm, hipStream_t s) {
+                              int mode, int ppm, hipStream_t s, const BankIdx* bank) {
     constexpr int L = ColGeom<H, 1>::L;
     if constexpr (L <= 64) {
         // column pairs with 16-byte accesses (k_pass_b2): measured faster up to H = 512 (C2: pass B
@@ -550,6 +583,13 @@ template <int H> int pass_b_h(const cf* spec, cf* out, const float* fcT, const c
         if (mode == 0 && N >= 16 && env_int("ADMM_PASSB_PAIR", H <= 512 ? 1 : 0)) {
             using G = ColGeom<H, 8>;
             const int colblocks = N / 16;
+            if (bank) {
+                if (int e = set_lds(k_pass_b2<H, 8, BankIdx>, G::lds_bytes())) return e;
+                hipLaunchKernelGGL((k_pass_b2<H, 8, BankIdx>), dim3((unsigned)((long long)P * colblocks)), dim3(G::NT),
+                                   G::lds_bytes(), s, spec, out, fcT, twH, N, colblocks, ppm, passb_order(H),
+                                   env_int("ADMM_PASSB_FPACK", 1) ? 1 : 0, *bank);
+                return launch_check("k_pass_b2<bank>");
+            }
             if (int e = set_lds(k_pass_b2<H, 8>, G::lds_bytes())) return e;
             hipLaunchKernelGGL((k_pass_b2<H, 8>), dim3((unsigned)((long long)P * colblocks)), dim3(G::NT), G::lds_bytes(),
                                s, spec, out, fcT, twH, N, colblocks, ppm, passb_order(H), env_int("ADMM_PASSB_FPACK", 1) ? 1 : 0);
@@ -557,26 +597,26 @@ template <int H> int pass_b_h(const cf* spec, cf* out, const float* fcT, const c
         }
         int C = env_int("ADMM_PASSB_C", 8);
         if (C > N) C = N;
-        if (C >= 16) return pass_b_hc<H, 16>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
-        return pass_b_hc<H, 8>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
+        if (C >= 16) return pass_b_hc<H, 16>(spec, out, fcT, mT, twH, N, P, mode, ppm, s, bank);
+        return pass_b_hc<H, 8>(spec, out, fcT, mT, twH, N, P, mode, ppm, s, bank);
     } else if constexpr (L == 128) {
-        return pass_b_hc<H, 8>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
+        return pass_b_hc<H, 8>(spec, out, fcT, mT, twH, N, P, mode, ppm, s, bank);
     } else {
-        return pass_b_hc<H, 4>(spec, out, fcT, mT, twH, N, P, mode, ppm, s);
+        return pass_b_hc<H, 4>(spec, out, fcT, mT, twH, N, P, mode, ppm, s, bank);
     }
 }
 
 // column pass; out == spec (in place) or a separate buffer
 // ppm: planes per module (module m = plane / ppm uses Wiener factor m); ppm = P for one module
 int pass_b_oop(int H, const cf* spec, cf* out, const float* fcT, const cf* mT, const cf* twH, int N, int P, int mode,
-               hipStream_t s, int ppm = 0) {
+               hipStream_t s, int ppm = 0, const BankIdx* bank = nullptr) {
     if (ppm <= 0) ppm = P;
-    return with_col(H, [&](auto h) { return pass_b_h<decltype(h)::value>(spec, out, fcT, mT, twH, N, P, mode, ppm, s); });
+    return with_col(H, [&](auto h) { return pass_b_h<decltype(h)::value>(spec, out, fcT, mT, twH, N, P, mode, ppm, s, bank); });
 }
 
 int pass_b(int H, cf* spec, const float* fcT, const cf* mT, const cf* twH, int N, int P, int mode, hipStream_t s,
-           int ppm = 0) {
-    return pass_b_oop(H, spec, spec, fcT, mT, twH, N, P, mode, s, ppm);
+           int ppm = 0, const BankIdx* bank = nullptr) {
+    return pass_b_oop(H, spec, spec, fcT, mT, twH, N, P, mode, s, ppm, bank);
 }
 
 // cross-spectrum partials sum_{p in group} conj(colFFT U_p) colFFT V_p  -> part[g][N+1][H]
@@ -628,10 +668,55 @@ int validate(const admm_tv_desc* d) {
     return 0;
 }
 
+// what a PSF bank refuses (after validate, before any other check, in every entry point, size query and
+// admm_tv_path alike).  train: a training entry point; f64: an *_f64 entry point
+int bank_check(const admm_tv_desc& d, bool train = false, bool f64 = false) {
+    if (!is_bank(d)) return 0;
+    if (f64 || is_f64(d)) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: fp32 only (ADMM_TV_FLAG_F64 / an _f64 entry point)");
+    if (train) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: inference only (training with a bank is not implemented)");
+    if (d.flags & ADMM_TV_FLAG_PSF_GRAD) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: no PSF gradient (ADMM_TV_FLAG_PSF_GRAD)");
+    if (d.kh == 0) return fail(ADMM_TV_EINVAL, "PSF bank without a PSF (kh == 0)");
+    if (d.groups > 1) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: groups > 1 (one solve per module)");
+    if (d.allreduce) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: no cross-rank all-reduce hook");
+    const long long T = ((d.flags & ADMM_TV_FLAG_PSF_PER_IMAGE) ? d.B : 1) * ((d.flags & ADMM_TV_FLAG_PSF_PER_CHANNEL) ? d.C : 1);
+    if (T > kBankMax || d.B > 0x7fffffffLL || d.C > 0x7fffffffLL)
+        return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: more than 65,535 PSFs");
+    return 0;
+}
+
 // the multiplier tables carry the transforms' normalisation: the packed power-of-two row
 // transforms produce 2 rfft, the generic ones rfft
 double spectra_scale(int H, int W) {
     return (supported_hw(H, W) ? 0.5 : 1.0) / ((double)H * (double)W);
+}
+
+// The PSF tables of a bank (setup's PSF part, after its twiddle tables): every kernel takes its table from the
+// grid's second dimension, so a bank of B C PSFs is set up by the launches one PSF takes.  rho is the bank's.
+// bank_spectra: the Wiener factors into fcT (T tables) and the H_t multipliers (with their smooth-size copy).
+int bank_spectra(const admm_tv_desc& d, const Layout& Lo, void* ws, const float* rho, float* fcT, hipStream_t s) {
+    const int H = (int)d.H, W = (int)d.W, N = W / 2, nt = 256, n = (N + 1) * H;
+    const unsigned T = (unsigned)bank_of(d).T;
+    hipLaunchKernelGGL(k_spectra_bank, dim3((n + nt - 1) / nt, T), dim3(nt), 0, s, at<double2>(ws, Lo.G),
+                       at<double2>(ws, Lo.twHd), rho, fcT, at<cf>(ws, Lo.mT), d.kh, H, N, W, spectra_scale(H, W));
+    if (int e = launch_check("k_spectra_bank")) return e;
+    if (Lo.mixed) return hip_code(admm_mixed::mt_mixed(at<cf>(ws, Lo.mT), at<cf>(ws, Lo.mM), H, N, s, (int)T), "k_mt_mixed_bank");
+    return 0;
+}
+int setup_bank(const admm_tv_desc& d, const Layout& Lo, void* ws, const float* kern, const float* rho, hipStream_t s) {
+    const int H = (int)d.H, W = (int)d.W, N = W / 2, k = d.kh, nt = 256, n = (N + 1) * H;
+    const unsigned T = (unsigned)bank_of(d).T;
+    hipLaunchKernelGGL(k_psf_rows_bank, dim3((k * (N + 1) + nt - 1) / nt, T), dim3(nt), 0, s, kern, at<double2>(ws, Lo.G), k,
+                       N, W);
+    if (int e = launch_check("k_psf_rows_bank")) return e;
+    if (!rho) return 0;
+    float* fc = at<float>(ws, Lo.fcT);
+    if (int e = bank_spectra(d, Lo, ws, rho, fc, s)) return e;
+    if (!Lo.gen) {  // the packed copies follow the T tables
+        hipLaunchKernelGGL(k_fc_pack_bank, dim3((n + nt - 1) / nt, T), dim3(nt), 0, s, fc, fc + (size_t)T * n, H, N, col_e(H));
+        if (int e = launch_check("k_fc_pack_bank")) return e;
+    }
+    if (Lo.mixed) return hip_code(admm_mixed::fc_mixed(fc, at<float>(ws, Lo.fcM), H, N, s, (int)T), "k_fc_mixed_bank");
+    return 0;
 }
 
 // setup: twiddle tables, PSF spectrum, Wiener factor (if rho given), centred-PSF multiplier
@@ -652,6 +737,9 @@ int setup(const admm_tv_desc& d, const Layout& Lo, void* ws, const T* kern, cons
                                at<cf>(ws, dim == 0 ? Lo.twW : Lo.twH), pl);
             if (int e = launch_check("k_blue_tables")) return e;
         }
+    }
+    if constexpr (std::is_same<T, float>::value) {
+        if (is_bank(d)) return setup_bank(d, Lo, ws, kern, rho, s);
     }
     if (k > 0) {
         const int n = k * (N + 1);
@@ -848,7 +936,9 @@ int psf_transpose_into(const admm_tv_desc& d, const Layout& Lo, void* ws, const 
     cf* twW = at<cf>(ws, Lo.twW);
     int e = with_row(N, [&](auto ops) { return decltype(ops)::r2c(xin, spec, twW, rows, s); });
     if (e) return e;
-    if ((e = pass_b(H, spec, at<float>(ws, Lo.fcT), at<cf>(ws, Lo.mT), at<cf>(ws, Lo.twH), N, (int)(d.B * d.C), mode, s)))
+    const BankIdx bk = bank_of(d);  // a PSF bank: each plane's own multiplier
+    if ((e = pass_b(H, spec, at<float>(ws, Lo.fcT), at<cf>(ws, Lo.mT), at<cf>(ws, Lo.twH), N, (int)(d.B * d.C), mode, s,
+                    is_bank(d) ? bank_run(d) : 0, is_bank(d) ? &bk : nullptr)))
         return e;
     return with_row(N, [&](auto ops) { return decltype(ops)::c2r(spec, bb, twW, rows, s, pl); });
 }
@@ -1335,9 +1425,45 @@ template <int S> int gcol_mm_launch(const GColMMArgs& a, size_t lds, hipStream_t
 inline int mm_dbg() { return ADMM_MM_DBG_BUILD ? env_int("ADMM_MM_DBG", 0) : 0; }
 
 // mm: the layout's column-pass plan (Layout::mm; its factor copy was sized and written for it)
+// the column pass of a PSF bank's planes [p0, p0 + P) (k_gcol_bank: modes 0 and 1, the LDS column pass)
+template <int MODE, int BM, bool TWG, bool GLB>
+int gcol_bank_launch(const GColBankArgs& a, size_t lds, dim3 grid, hipStream_t s) {
+    if constexpr (BM == 0 && !GLB) {
+        if (gen_wide(a.plan.n, a.plan)) {
+            if (int e = set_lds(k_gcol_bank<MODE, BM, TWG, kGenWide>, lds)) return e;
+            hipLaunchKernelGGL((k_gcol_bank<MODE, BM, TWG, kGenWide>), grid, dim3(kGenWide), lds, s, a);
+            return launch_check("k_gcol_bank");
+        }
+    }
+    if (int e = set_lds(k_gcol_bank<MODE, BM, TWG, GNT, GLB>, lds)) return e;
+    hipLaunchKernelGGL((k_gcol_bank<MODE, BM, TWG, GNT, GLB>), grid, dim3(GLB ? GNT : gen_threads("ADMM_GCOL_NT")), lds, s, a);
+    return launch_check("k_gcol_bank");
+}
+
+// bank, p0: a PSF bank's table index and the solve's plane that the launch's plane 0 is (fp32, modes 0 and 1)
 template <class T>
 int gcol(cx_t<T>* spec, cx_t<T>* dump, const T* fcT, const cx_t<T>* mT, const cx_t<T>* tw, int H, int W, long long P,
-         int mode, hipStream_t s, cx_t<T>* gscr, const MMPlan& mm, int ldw = 0) {
+         int mode, hipStream_t s, cx_t<T>* gscr, const MMPlan& mm, int ldw = 0, const BankIdx* bank = nullptr,
+         long long p0 = 0) {
+    if constexpr (!kF64<T>) {
+        if (bank) {
+            if (mm.ok || dump || mode > 1) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: the LDS column pass, inference only");
+            const GPlan pl = make_plan(H, false);
+            GLB_CHECK(pl, gscr)
+            const int Wh = W / 2 + 1, cols = gcol_cols(H, pl);
+            if (ldw && ldw != Wh) return fail(ADMM_TV_EINVAL, "padded spectrum pitch without the matrix-core column pass");
+            const int colblocks = (Wh + cols - 1) / cols;
+            const GColBankArgs a{{spec, nullptr, fcT, mT, tw, pl, Wh, cols, colblocks, P, gscr}, *bank, p0};
+            const size_t lds = glds(H, cols, pl);
+            const dim3 grid = gen_grid(P * colblocks, pl, sizeof(cf));
+            return with_plan(pl, [&](auto bm, auto twg, auto glb) {
+                constexpr int BM = decltype(bm)::value;
+                constexpr bool TWG = decltype(twg)::value, GLB = decltype(glb)::value;
+                return mode == 0 ? gcol_bank_launch<0, BM, TWG, GLB>(a, lds, grid, s)
+                                 : gcol_bank_launch<1, BM, TWG, GLB>(a, lds, grid, s);
+            });
+        }
+    }
     if constexpr (!kF64<T>) {
         const MMPlan m = mm;
         if (mode == 0 && m.ok) {  // the factor's [H][Wh] copy follows fcT (setup, k_fc_transpose)
@@ -1384,8 +1510,9 @@ int gapply(const T* img_in, T* img_out, cx_t<T>* spec, const Layout& Lo, void* w
     C* twW = at<C>(ws, Lo.twW);
     C* gs = at<C>(ws, Lo.gscr);
     if (int e = grow_fwd(img_in, spec, twW, W, rows, s, gs)) return e;
+    const BankIdx bk = bank_of(d);  // a PSF bank: each plane's own multiplier
     if (int e = gcol<T>(spec, nullptr, at<T>(ws, Lo.fcT), at<C>(ws, Lo.mT), at<C>(ws, Lo.twH), H, W, P, mode, s, gs,
-                        Lo.mm))
+                        Lo.mm, 0, is_bank(d) ? &bk : nullptr))
         return e;
     return grow_inv<T>(spec, img_out, twW, W, rows, s, gs, Lo.mmr);
 }
@@ -1587,6 +1714,8 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
     // first iteration's u input; the odd-length row pass does not know about state, so such a solve keeps
     // the three-launch iteration
     const bool stateful = sio != nullptr, sin = sio && sio->in, sout = sio && sio->out;
+    const BankIdx bank = bank_of(d);
+    const BankIdx* const bankp = is_bank(d) ? &bank : nullptr;
     const T* r1img = bimg;
     if constexpr (!kF64<T>) {
         if (sin) {
@@ -1643,7 +1772,9 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         const bool last = it == d.maxit;
         {
             ProfScope ps(1, st);
-            if (int e = gcol<T>(cspec, keep_t ? hv.r(it) : nullptr, fcT, mT, twH, H, W, np, 0, st, gs, Lo.mm, ld)) return e;
+            // (a PSF bank: the table index comes from the solve's plane p0 + p, not the part's)
+            if (int e = gcol<T>(cspec, keep_t ? hv.r(it) : nullptr, fcT, mT, twH, H, W, np, 0, st, gs, Lo.mm, ld, bankp, p0))
+                return e;
             if (int e = grow_inv<T>(cspec, last ? cout : cx, twW, W, crows, st, gs, Lo.mmr, ld)) return e;
         }
         if (last && !train) break;
@@ -1832,7 +1963,12 @@ struct Pow2Ops : FusedOps {
     }
     // column pass of np planes, ppm per module, from `in` into `out` (the same buffer, or -- PSF-gradient
     // training -- r_k's kept spectra); the modules' Wiener factors follow one another from fcT (g0 == 0)
+    // (a PSF bank, one module: each plane's table instead, the kernels' BankIdx instances)
     int col(const cf* in, cf* out, long long np, long long ppm, int /*g0*/, hipStream_t s) const {
+        if (is_bank(d)) {
+            const BankIdx bk = bank_of(d);
+            return pass_b_oop(H, in, out, fcT, mT, twH, N, (int)np, 0, s, bank_run(d), &bk);
+        }
         return pass_b_oop(H, in, out, fcT, mT, twH, N, (int)np, 0, s, (int)ppm);
     }
     // cross-spectrum partials for the PSF gradient (weighted: the A terms, which k_xspec_reduce weights by
@@ -1882,7 +2018,12 @@ struct MixedOps : FusedOps {
     }
     // one module's planes with module g0's factor, from `in` into `out` (the same buffer, or -- PSF-gradient
     // training -- r_k's kept spectra)
+    // (a PSF bank, one module: one launch over all planes, each with its table)
     int col(const cf* in, cf* out, long long np, long long, int g0, hipStream_t s) const {
+        if (is_bank(d)) {
+            const BankIdx bk = bank_of(d);
+            return hip_code(admm_mixed::pass_b(H, in, out, fcM, twH, N, np, s, &bk), "k_pass_b_m<bank>");
+        }
         return hip_code(admm_mixed::pass_b(H, in, out, fcM + (size_t)g0 * (2 * N + 1) * H, twH, N, np, s), "k_pass_b_m");
     }
     // Cross spectra of two sets of packed row spectra.  They carry the packed transforms' factor 2 each, as on
@@ -1914,7 +2055,10 @@ struct MixedOps : FusedOps {
         const long long P = d.B * d.C;
         if (env_int("ADMM_MIXED_BGEN", 0)) return gapply<float>(xin, bb, spec, Lo, ws, d, 1, s);
         if (int e = r2c(xin, spec, P * H, s)) return e;
-        if (int e = hip_code(admm_mixed::pass_b_cm(H, spec, at<cf>(ws, Lo.mM), twH, N, P, s), "k_pass_b_m<cm>")) return e;
+        const BankIdx bk = bank_of(d);
+        if (int e = hip_code(admm_mixed::pass_b_cm(H, spec, at<cf>(ws, Lo.mM), twH, N, P, s, is_bank(d) ? &bk : nullptr),
+                             "k_pass_b_m<cm>"))
+            return e;
         return c2r(spec, bb, P * H, s);
     }
     // x^_in = H_t^T b^ (the conjugate multiplier, generic transforms)
@@ -2507,6 +2651,7 @@ int admm_tv_supported_f64(int64_t H, int64_t W) { return f64_hw(H, W) ? 1 : 0; }
 
 int admm_tv_path(const admm_tv_desc* d, int train) {
     if (int e = validate(d)) return e;
+    if (int e = bank_check(*d, train == 1)) return e;
     if (train == 2) {  // admm_tv_forward_state: the fused paths, else the generic loop (also where the plain
                        // solve takes the odd-length row pass, which carries no state)
         if (int e = state_check(*d)) return e;
@@ -2529,6 +2674,7 @@ const char* admm_tv_last_error(void) { return g_err.c_str(); }
 
 int admm_tv_workspace_size(const admm_tv_desc* d, size_t* bytes) {
     if (int e = validate(d)) return e;
+    if (int e = bank_check(*d)) return e;
     if (!bytes) return fail(ADMM_TV_EINVAL, "null bytes");
     *bytes = make_layout(*d).total;
     return 0;
@@ -2537,6 +2683,7 @@ int admm_tv_workspace_size(const admm_tv_desc* d, size_t* bytes) {
 int admm_tv_forward(const admm_tv_desc* dp, const float* xin, const float* kern, const float* lam, const float* rho,
                     float* out, void* ws, size_t ws_bytes, void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp)) return e;
     if (is_f64(*dp)) return fail(ADMM_TV_EINVAL, "ADMM_TV_FLAG_F64: use admm_tv_forward_f64");
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
@@ -2547,6 +2694,7 @@ int admm_tv_forward(const admm_tv_desc* dp, const float* xin, const float* kern,
 
 int admm_tv_state_workspace_size(const admm_tv_desc* d, size_t* bytes) {
     if (int e = validate(d)) return e;
+    if (int e = bank_check(*d)) return e;
     if (int e = state_check(*d)) return e;
     if (!bytes) return fail(ADMM_TV_EINVAL, "null bytes");
     *bytes = make_layout(*d).total;  // the forward's regions serve: v lives in `out`, the iso norm in part / nsq
@@ -2557,6 +2705,7 @@ int admm_tv_forward_state(const admm_tv_desc* dp, const float* xin, const float*
                           const float* rho, const admm_tv_state* state_in, const admm_tv_state* state_out, float* out,
                           void* ws, size_t ws_bytes, void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp)) return e;
     if (int e = state_check(*dp)) return e;
     if (!xin || !out || !lam || !rho || (dp->kh > 0 && !kern)) return fail(ADMM_TV_EINVAL, "null pointer argument");
     for (const admm_tv_state* st : {state_in, state_out})
@@ -2570,6 +2719,7 @@ int admm_tv_forward_state(const admm_tv_desc* dp, const float* xin, const float*
 
 int admm_tv_history_size(const admm_tv_desc* d, size_t* bytes) {
     if (int e = validate(d)) return e;
+    if (int e = bank_check(*d, true)) return e;
     if (int e = grouped_train_check(*d)) return e;
     if (!bytes) return fail(ADMM_TV_EINVAL, "null bytes");
     *bytes = make_hist(*d).total;
@@ -2580,6 +2730,7 @@ int admm_tv_forward_train(const admm_tv_desc* dp, const float* xin, const float*
                           const float* rho, float* out, void* hist, size_t hist_bytes, void* ws, size_t ws_bytes,
                           void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp, true)) return e;
     if (int e = grouped_train_check(*dp)) return e;
     if (is_f64(*dp)) return fail(ADMM_TV_EINVAL, "ADMM_TV_FLAG_F64: use admm_tv_forward_train_f64");
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
@@ -2594,6 +2745,7 @@ int admm_tv_forward_train(const admm_tv_desc* dp, const float* xin, const float*
 
 int admm_tv_backward_workspace_size(const admm_tv_desc* d, size_t* bytes) {
     if (int e = validate(d)) return e;
+    if (int e = bank_check(*d, true)) return e;
     if (int e = grouped_train_check(*d)) return e;
     if (!bytes) return fail(ADMM_TV_EINVAL, "null bytes");
     *bytes = make_bwd_layout(*d).total;
@@ -2604,6 +2756,7 @@ int admm_tv_backward(const admm_tv_desc* dp, const float* xin, const float* kern
                      const float* rho, const float* gout, const void* hist, size_t hist_bytes, float* gxin,
                      float* glam, float* grho, float* gkern, void* ws, size_t ws_bytes, void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp, true)) return e;
     if (int e = grouped_train_check(*dp)) return e;
     if (is_f64(*dp)) return fail(ADMM_TV_EINVAL, "ADMM_TV_FLAG_F64: use admm_tv_backward_f64");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
@@ -2615,6 +2768,7 @@ int admm_tv_backward(const admm_tv_desc* dp, const float* xin, const float* kern
 int admm_tv_psf_transpose(const admm_tv_desc* dp, const float* xin, const float* kern, float* out, void* ws,
                           size_t ws_bytes, void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp)) return e;
     if (is_f64(*dp)) return fail(ADMM_TV_EINVAL, "ADMM_TV_FLAG_F64: fp32 entry point");
     const admm_tv_desc d = *dp;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2632,6 +2786,14 @@ int admm_tv_psf_transpose(const admm_tv_desc* dp, const float* xin, const float*
     const int n = (N + 1) * H;
     // k_spectra needs a rho pointer: point it at a zeroed float inside the workspace (fcT region)
     HIPCHK(hipMemsetAsync(at<float>(ws, Lo.fcT), 0, sizeof(float), s));
+    if (is_bank(d)) {
+        // a bank: every table's multiplier (the unused factors, T (N + 1) H floats, fit the spec[1] image:
+        // T <= B C, N + 1 <= W); a smooth size runs the mixed transforms, whose multiplier index the solve uses
+        if (int e = bank_spectra(d, Lo, ws, at<float>(ws, Lo.fcT), at<float>(ws, Lo.spec[1]), s)) return e;
+        if (Lo.mixed) return MixedOps(d, Lo, ws).make_b(xin, out, at<cf>(ws, Lo.spec[0]), false, s);
+        if (Lo.gen) return gapply(xin, out, at<cf>(ws, Lo.spec[0]), Lo, ws, d, 1, s);
+        return psf_transpose_into(d, Lo, ws, xin, out, at<cf>(ws, Lo.spec[0]), 1, s);
+    }
     hipLaunchKernelGGL(k_spectra<float>, dim3((n + 255) / 256), dim3(256), 0, s, at<double2>(ws, Lo.G),
                        at<double2>(ws, Lo.twHd), at<float>(ws, Lo.fcT), at<float>(ws, Lo.spec[1]),
                        at<cf>(ws, Lo.mT), d.kh, H, N, W, nullptr, spectra_scale(H, W));
@@ -2643,6 +2805,7 @@ int admm_tv_psf_transpose(const admm_tv_desc* dp, const float* xin, const float*
 int admm_tv_forward_f64(const admm_tv_desc* dp, const double* xin, const double* kern, const double* lam,
                         const double* rho, double* out, void* ws, size_t ws_bytes, void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp, false, true)) return e;
     if (!is_f64(*dp)) return fail(ADMM_TV_EINVAL, "admm_tv_forward_f64 needs ADMM_TV_FLAG_F64");
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
@@ -2655,6 +2818,7 @@ int admm_tv_forward_train_f64(const admm_tv_desc* dp, const double* xin, const d
                               const double* rho, double* out, void* hist, size_t hist_bytes, void* ws, size_t ws_bytes,
                               void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp, false, true)) return e;
     if (!is_f64(*dp)) return fail(ADMM_TV_EINVAL, "admm_tv_forward_train_f64 needs ADMM_TV_FLAG_F64");
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
@@ -2670,6 +2834,7 @@ int admm_tv_backward_f64(const admm_tv_desc* dp, const double* xin, const double
                          const double* rho, const double* gout, const void* hist, size_t hist_bytes, double* gxin,
                          double* glam, double* grho, double* gkern, void* ws, size_t ws_bytes, void* stream) {
     if (int e = validate(dp)) return e;
+    if (int e = bank_check(*dp, false, true)) return e;
     if (!is_f64(*dp)) return fail(ADMM_TV_EINVAL, "admm_tv_backward_f64 needs ADMM_TV_FLAG_F64");
     if ((!gout && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");

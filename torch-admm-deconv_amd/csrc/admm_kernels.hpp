@@ -140,9 +140,23 @@ __global__ void k_tables(C* __restrict__ twW, C* __restrict__ twH, double2* __re
     }
 }
 
+// PSF bank (ADMM_TV_FLAG_PSF_PER_IMAGE / _PER_CHANNEL): kern holds (Bk, Ck, k, k) PSFs and every table
+// derived from one (G, fcT and its copies, mT) exists T = Bk Ck times, table after table.  Plane p = b C + c
+// uses table (Bk > 1 ? b : 0) Ck + (Ck > 1 ? c : 0) = (p / C) sb + (p % C) sc.
+struct BankIdx {
+    int C, sb, sc, T;
+    __host__ __device__ int tab(long long p) const { return (int)(p / C) * sb + (int)(p % C) * sc; }
+};
+// for kernels that take the bank as a trailing argument pack (empty: the shared PSF): plane p's table, and the
+// number of tables (`one`: what the kernel computes without a bank)
+__device__ __forceinline__ int bank_tab(long long) { return 0; }
+__device__ __forceinline__ int bank_tab(long long p, const BankIdx& bk) { return bk.tab(p); }
+__device__ __forceinline__ int bank_tables(int one) { return one; }
+__device__ __forceinline__ int bank_tables(int, const BankIdx& bk) { return bk.T; }
+
 // G[a][kx] = sum_b kern[a][b] exp(-2 pi i b kx / W), kx in [0, N], in fp64
-template <class T = float>
-__global__ void k_psf_rows(const T* __restrict__ kern, double2* __restrict__ G, int k, int N, int W) {
+template <class T>
+__device__ __forceinline__ void psf_rows_body(const T* __restrict__ kern, double2* __restrict__ G, int k, int N, int W) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k * (N + 1)) return;
     const int a = i / (N + 1), kx = i % (N + 1);
@@ -157,14 +171,23 @@ __global__ void k_psf_rows(const T* __restrict__ kern, double2* __restrict__ G, 
     }
     G[i] = make_double2(re, im);
 }
+template <class T = float>
+__global__ void k_psf_rows(const T* __restrict__ kern, double2* __restrict__ G, int k, int N, int W) {
+    psf_rows_body<T>(kern, G, k, N, W);
+}
+// a bank: table blockIdx.y from PSF blockIdx.y
+static __global__ void k_psf_rows_bank(const float* __restrict__ kern, double2* __restrict__ G, int k, int N, int W) {
+    psf_rows_body<float>(kern + (size_t)blockIdx.y * k * k, G + (size_t)blockIdx.y * k * (N + 1), k, N, W);
+}
 
 // fcT[kx][ky] = scale / (|sigma|^2 + rho (|Dx^|^2 + |Dy^|^2));
 // mT[kx][ky] = scale * sigma * exp(+2 pi i c (ky/H + kx/W))  (centred PSF, c = k/2)
 // scale = 1/(2HW) for the packed power-of-two path, 1/(HW) for the generic path
-template <class T = float>
-__global__ void k_spectra(const double2* __restrict__ G, const double2* __restrict__ twHd,
-                          const T* __restrict__ rho_p, T* __restrict__ fcT, cx_t<T>* __restrict__ mT, int k,
-                          int H, int N, int W, double2* __restrict__ sigma_out, double scale) {
+template <class T>
+__device__ __forceinline__ void spectra_body(const double2* __restrict__ G, const double2* __restrict__ twHd,
+                                             const T* __restrict__ rho_p, T* __restrict__ fcT,
+                                             cx_t<T>* __restrict__ mT, int k, int H, int N, int W,
+                                             double2* __restrict__ sigma_out, double scale) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (N + 1) * H) return;
     const int kx = i / H, ky = i % H;
@@ -191,6 +214,20 @@ __global__ void k_spectra(const double2* __restrict__ G, const double2* __restri
         sincospi(2.0 * (double)(ph % HW) / (double)HW, &s, &co);
         mT[i] = mkx<T>((T)((sr * co - si * s) * scale), (T)((sr * s + si * co) * scale));
     }
+}
+template <class T = float>
+__global__ void k_spectra(const double2* __restrict__ G, const double2* __restrict__ twHd,
+                          const T* __restrict__ rho_p, T* __restrict__ fcT, cx_t<T>* __restrict__ mT, int k,
+                          int H, int N, int W, double2* __restrict__ sigma_out, double scale) {
+    spectra_body<T>(G, twHd, rho_p, fcT, mT, k, H, N, W, sigma_out, scale);
+}
+// a bank: table blockIdx.y of G, fcT and mT (one rho for the bank)
+static __global__ void k_spectra_bank(const double2* __restrict__ G, const double2* __restrict__ twHd,
+                                      const float* __restrict__ rho_p, float* __restrict__ fcT, cf* __restrict__ mT,
+                                      int k, int H, int N, int W, double scale) {
+    const size_t n = (size_t)(N + 1) * H;
+    spectra_body<float>(G + (size_t)blockIdx.y * k * (N + 1), twHd, rho_p, fcT + blockIdx.y * n, mT + blockIdx.y * n, k, H,
+                        N, W, nullptr, scale);
 }
 
 // ---------------------------------------------------------------------------
@@ -363,6 +400,14 @@ static __global__ void k_fc_pack(const float* __restrict__ fcT, float* __restric
     const int L = H / E, kx = i / H, r = i % H, t = r / E, j = r % E;
     fcP[i] = fcT[(size_t)kx * H + t + L * j];
 }
+// a bank: table blockIdx.y (fcT and fcP hold the bank's tables one after another)
+static __global__ void k_fc_pack_bank(const float* __restrict__ fcT, float* __restrict__ fcP, int H, int N, int E) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (N + 1) * H) return;
+    const size_t o = (size_t)blockIdx.y * (N + 1) * H;
+    const int L = H / E, kx = i / H, r = i % H, t = r / E, j = r % E;
+    fcP[o + i] = fcT[o + (size_t)kx * H + t + L * j];
+}
 
 // XCD-aware remap (T1): blocks are dealt round-robin over the 8 XCDs; give each XCD a
 // contiguous range of logical ids so neighbouring column blocks (which share 128-B
@@ -416,11 +461,16 @@ __device__ __forceinline__ void pb_tile(unsigned lb, int colblocks, int order, b
 // for all of them, so the Wiener-factor table is read once per gp planes instead of once per
 // plane (at C3 the per-plane reads were 0.40 GB of extra requests per launch, served by the
 // Infinity Cache, +51 % of pass B's reads).
-template <int H, int C, int MODE>
+// BK = BankIdx (k_pass_b<H, C, MODE, BankIdx>, one trailing argument): a PSF bank -- the multipliers come from
+// the table of the block's planes (gp planes of one table: the host picks gp = 1, or a divisor of C for a
+// per-image bank; ppm is unused), MODE 1 / 2 included.  An empty pack is the shared-PSF kernel: the same
+// signature and, the bank's terms being compile-time branches, the same code as without the parameter.
+template <int H, int C, int MODE, class... BK>
 __global__ void __launch_bounds__(C * (H / RowCfg<H>::E), pb_minw(C * (H / RowCfg<H>::E), sizeof(cf) * (H + (size_t)H * C)))
     k_pass_b(const cf* spec_in, cf* spec_out, const float* __restrict__ fcT, const cf* __restrict__ mT,
              const cf* __restrict__ twH_g, int N, int colblocks, int ppm, int order, int fpack, int gp, int P,
-             int pmode) {
+             int pmode, BK... bk) {
+    constexpr bool BANK = sizeof...(BK) > 0;
     using G = ColGeom<H, C>;
     constexpr int E = G::E, L = G::L;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -438,7 +488,13 @@ __global__ void __launch_bounds__(C * (H / RowCfg<H>::E), pb_minw(C * (H / RowCf
     if (pmode & 1) pg = (int)(gridDim.x / (unsigned)colblocks) - 1 - pg;
     const int col = cb * C + c;
     const int p0 = pg * gp;
-    if (MODE == 0) fcT += (size_t)(p0 / ppm) * (N + 1) * H;  // this module's Wiener factor
+    if constexpr (BANK) {  // this plane group's table
+        const size_t to = (size_t)bank_tab(p0, bk...) * (N + 1) * H;
+        if (MODE == 0) fcT += to;
+        else mT += to;
+    } else {
+        if (MODE == 0) fcT += (size_t)(p0 / ppm) * (N + 1) * H;  // this module's Wiener factor
+    }
     const int voff = (t * N + col) * (int)sizeof(cf);
     const int sstep = L * N * (int)sizeof(cf);
     using MT = typename std::conditional<MODE == 0, float, cf>::type;
@@ -448,7 +504,7 @@ __global__ void __launch_bounds__(C * (H / RowCfg<H>::E), pb_minw(C * (H / RowCf
         if (MODE == 0 && fpack) {
             // the packed copy of the Wiener factors (k_fc_pack, after the G tables of this region): a
             // thread's E factors are contiguous, E/4 16-byte loads instead of E 4-byte ones
-            const float* fcP = fcT + (size_t)(P / ppm) * (N + 1) * H;  // fcT: this module's
+            const float* fcP = fcT + (size_t)bank_tables(P / ppm, bk...) * (N + 1) * H;  // fcT: this module's
             const float4* qq = reinterpret_cast<const float4*>(fcP + ((size_t)col * L + t) * E);
     #pragma unroll
             for (int j = 0; j < E / 4; ++j) {
@@ -540,10 +596,12 @@ __device__ __forceinline__ void bstore_f4(rsrc_t r, int voff, int soff, float4 v
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(V4, v), r, voff, soff, 0);
 }
 
-template <int H, int CP>
+// (BK = BankIdx: a PSF bank, as k_pass_b's)
+template <int H, int CP, class... BK>
 __global__ void __launch_bounds__(CP * (H / RowCfg<H>::E), PASSB2_MINW)
     k_pass_b2(const cf* spec_in, cf* spec_out, const float* __restrict__ fcT, const cf* __restrict__ twH_g, int N,
-              int colblocks, int ppm, int order, int fpack) {
+              int colblocks, int ppm, int order, int fpack, BK... bk) {
+    constexpr bool BANK = sizeof...(BK) > 0;
     using G = ColGeom<H, CP>;
     constexpr int E = G::E, L = G::L;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -555,7 +613,8 @@ __global__ void __launch_bounds__(CP * (H / RowCfg<H>::E), PASSB2_MINW)
     int p, cb;
     pb_tile(xcd_remap(blockIdx.x, gridDim.x), colblocks, order, false, p, cb);
     const int col = cb * 2 * CP + 2 * cp;  // this thread's columns: col, col + 1
-    fcT += (size_t)(p / ppm) * (N + 1) * H;  // this module's Wiener factor
+    if constexpr (BANK) fcT += (size_t)bank_tab(p, bk...) * (N + 1) * H;  // this plane's table
+    else fcT += (size_t)(p / ppm) * (N + 1) * H;  // this module's Wiener factor
     const rsrc_t rs = make_rsrc(spec_in + (size_t)p * H * N, (unsigned)((size_t)H * N * sizeof(cf)));
     const rsrc_t ro = make_rsrc(spec_out + (size_t)p * H * N, (unsigned)((size_t)H * N * sizeof(cf)));
     const int voff = (t * N + col) * (int)sizeof(cf);
@@ -572,7 +631,7 @@ __global__ void __launch_bounds__(CP * (H / RowCfg<H>::E), PASSB2_MINW)
     const rsrc_t rm = make_rsrc(fcT, (unsigned)((size_t)(N + 1) * H * sizeof(float)));
     const int mo = (col * H + t) * (int)sizeof(float);
     // packed Wiener factors (k_fc_pack): a thread's E factors of a column are contiguous
-    const float* fcP = fcT + (size_t)(gridDim.x / colblocks / ppm) * (N + 1) * H;  // fcT: this module's
+    const float* fcP = fcT + (size_t)bank_tables(gridDim.x / colblocks / ppm, bk...) * (N + 1) * H;  // fcT: this module's
     auto packed = [&](int c, float (&m)[E]) {
         const float4* q = reinterpret_cast<const float4*>(fcP + ((size_t)c * L + t) * E);
 #pragma unroll
@@ -628,6 +687,7 @@ __global__ void __launch_bounds__(CP * (H / RowCfg<H>::E), PASSB2_MINW)
 #pragma unroll
     for (int j = 0; j < E; ++j) bstore_f4(ro, voff, j * sstep, make_float4(v0[j].x, v0[j].y, v1[j].x, v1[j].y));
 }
+
 
 // ---------------------------------------------------------------------------
 // pass A: the fused row pass of one ADMM iteration, one sub-group per strip of R rows

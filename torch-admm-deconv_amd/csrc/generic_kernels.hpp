@@ -601,6 +601,12 @@ template <class T> struct GColArgsT {
     cx_t<T>* gscr;        // plan.glb: the blocks' scratch slots, 2 H cols values each
 };
 using GColArgs = GColArgsT<float>;
+// the column pass of a PSF bank (k_gcol_bank): fcT / mT hold bank.T tables, plane p of the launch is plane
+// p0 + p of the solve (a solve split into plane parts launches each part on its own) and takes that plane's table
+struct GColBankArgs : GColArgsT<float> {
+    BankIdx bank;
+    long long p0;
+};
 
 // occupancy hint of the column pass with Bluestein stages of size 256 (waves per SIMD; A/B knob
 // -DADMM_GCOL_MINW=4 caps its VGPRs at 128)
@@ -609,9 +615,11 @@ using GColArgs = GColArgsT<float>;
 #endif
 constexpr int gcol_minw(int bm) { return bm == 256 ? ADMM_GCOL_MINW : 1; }
 
-template <int MODE, int BM, class T>
+// BANK: the multipliers from the table of the solve's plane p0 + p (GColBankArgs)
+template <int MODE, int BM, bool BANK = false, class T>
 __device__ __forceinline__ void gcol_item(const GColArgsT<T>& a, cx_t<T>* A, cx_t<T>* B, cx_t<T>* X,
-                                          const cx_t<T>* tw, long long item) {
+                                          const cx_t<T>* tw, long long item, const BankIdx bk = BankIdx{},
+                                          long long p0 = 0) {
     using C = cx_t<T>;
     const int H = a.plan.n, Wh = a.Wh, cols = a.cols;
     const int lgc = __ffs(cols) - 1;  // cols is a power of two
@@ -634,10 +642,12 @@ __device__ __forceinline__ void gcol_item(const GColArgsT<T>& a, cx_t<T>* A, cx_
         }
     }
     if constexpr (MODE == 3) return;
+    size_t fb = 0;  // the plane's table
+    if constexpr (BANK) fb = (size_t)bk.tab(p0 + p) * Wh * H;
     for (int idx = threadIdx.x; idx < H * cols; idx += blockDim.x) {
         const int ky = idx >> lgc, c = idx & (cols - 1);
         if (c >= nc) continue;
-        const size_t f = (size_t)(c0 + c) * H + ky;
+        const size_t f = fb + (size_t)(c0 + c) * H + ky;
         C v = res[ky * cols + c];
         if constexpr (MODE == 0) v = cscale(v, a.fcT[f]);
         else if constexpr (MODE == 1) v = cmul(v, a.mT[f]);
@@ -665,6 +675,22 @@ __global__ void __launch_bounds__(NT, gcol_minw(BM)) k_gcol(GColArgsT<T> a) {
         for (int i = threadIdx.x; i < H + a.plan.ntab; i += blockDim.x) twl[i] = a.tw[i];
     const C* tw = TWG ? a.tw : twl;
 #define ADMM_ITEM(item) gcol_item<MODE, BM>(a, A, B, X, tw, item)
+    ADMM_GEN_ITEMS(a.P * a.colblocks, 1, ADMM_ITEM)
+#undef ADMM_ITEM
+}
+// ... of a PSF bank (fp32 inference and H_t: MODE 0 and 1)
+template <int MODE, int BM, bool TWG, int NT = GNT, bool GLB = false>
+__global__ void __launch_bounds__(NT, gcol_minw(BM)) k_gcol_bank(GColBankArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int H = a.plan.n, cols = a.cols;
+    cf* twl = reinterpret_cast<cf*>(smem);
+    cf* A = line_bufs<GLB>(twl, TWG ? 0 : H + a.plan.ntab, a.gscr, 2 * (size_t)H * cols);
+    cf* B = A + (size_t)H * cols;
+    cf* X = GLB ? nullptr : B + (size_t)H * cols;
+    if constexpr (!TWG)
+        for (int i = threadIdx.x; i < H + a.plan.ntab; i += blockDim.x) twl[i] = a.tw[i];
+    const cf* tw = TWG ? a.tw : twl;
+#define ADMM_ITEM(item) gcol_item<MODE, BM, true>(a, A, B, X, tw, item, a.bank, a.p0)
     ADMM_GEN_ITEMS(a.P * a.colblocks, 1, ADMM_ITEM)
 #undef ADMM_ITEM
 }

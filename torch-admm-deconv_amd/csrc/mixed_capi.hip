@@ -229,7 +229,8 @@ int pass_b_cols(int H, int N) {
     return cols;
 }
 
-hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH, int N, long long P, hipStream_t s) {
+hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH, int N, long long P, hipStream_t s,
+                  const admm::BankIdx* bank) {
     return with_col(H, [&](auto h) {
         constexpr int HH = decltype(h)::value;
         // tile order (planes per group of the walk; pb_tile): plane-major below H = 1024; above, groups of
@@ -250,6 +251,14 @@ hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH,
                               : CC >= 8   ? (int)std::min<long long>(P, 1 << 30)
                                           : 2;
             const int colblocks = N / CC;
+            if (bank) {  // one launch over all planes, each with its table (inference: in place)
+                if (in != out) return hipErrorInvalidValue;
+                if (hipError_t e = lds(k_pass_b_m<HH, CC, false, false, admm::BankIdx>, G::lds_bytes())) return e;
+                hipLaunchKernelGGL((k_pass_b_m<HH, CC, false, false, admm::BankIdx>), dim3((unsigned)(P * colblocks)),
+                                   dim3(G::NT), G::lds_bytes(), s, out, fcM, twH, N, colblocks, order, fpack, nullptr,
+                                   nullptr, *bank);
+                return hipGetLastError();
+            }
             if (in != out) {  // out of place: the same tiles and arithmetic, the stores to `out`
                 if (hipError_t e = lds(k_pass_b_m<HH, CC, false, true>, G::lds_bytes())) return e;
                 hipLaunchKernelGGL((k_pass_b_m<HH, CC, false, true>), dim3((unsigned)(P * colblocks)), dim3(G::NT),
@@ -276,13 +285,21 @@ hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH,
     });
 }
 
-hipError_t pass_b_cm(int H, cf* spec, const cf* mM, const cf* twH, int N, long long P, hipStream_t s) {
+hipError_t pass_b_cm(int H, cf* spec, const cf* mM, const cf* twH, int N, long long P, hipStream_t s,
+                     const admm::BankIdx* bank) {
     return with_col(H, [&](auto h) {
         constexpr int HH = decltype(h)::value;
         auto go = [&](auto cc) {
             constexpr int CC = decltype(cc)::value;
             using G = MColG<HH, CC>;
             const int colblocks = N / CC;
+            if (bank) {
+                if (hipError_t e = lds(k_pass_b_m<HH, CC, true, false, admm::BankIdx>, G::lds_bytes())) return e;
+                hipLaunchKernelGGL((k_pass_b_m<HH, CC, true, false, admm::BankIdx>), dim3((unsigned)(P * colblocks)),
+                                   dim3(G::NT), G::lds_bytes(), s, spec, nullptr, twH, N, colblocks, 1, 0, mM, nullptr,
+                                   *bank);
+                return hipGetLastError();
+            }
             if (hipError_t e = lds(k_pass_b_m<HH, CC, true>, G::lds_bytes())) return e;
             hipLaunchKernelGGL((k_pass_b_m<HH, CC, true>), dim3((unsigned)(P * colblocks)), dim3(G::NT), G::lds_bytes(),
                                s, spec, nullptr, twH, N, colblocks, 1, 0, mM);
@@ -338,17 +355,27 @@ hipError_t xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N
     });
 }
 
-hipError_t mt_mixed(const cf* mT, cf* mM, int H, int N, hipStream_t s) {
+hipError_t mt_mixed(const cf* mT, cf* mM, int H, int N, hipStream_t s, int tables) {
     const long long n = (long long)H * (N + 1);
+    if (tables > 0) {
+        hipLaunchKernelGGL(k_mt_mixed_bank, dim3((unsigned)std::min<long long>(4096, (n + 255) / 256), (unsigned)tables),
+                           dim3(256), 0, s, mT, mM, H, N);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_mt_mixed, dim3((unsigned)std::min<long long>(4096, (n + 255) / 256)), dim3(256), 0, s, mT, mM,
                        H, N);
     return hipGetLastError();
 }
 
-hipError_t fc_mixed(const float* fcT, float* fcM, int H, int N, hipStream_t s) {
+hipError_t fc_mixed(const float* fcT, float* fcM, int H, int N, hipStream_t s, int tables) {
     const long long n = (long long)H * (2 * N + 1);
     const int C = pass_b_cols(H, N);
     if (C <= 0) return hipErrorInvalidValue;
+    if (tables > 0) {
+        hipLaunchKernelGGL(k_fc_mixed_bank, dim3((unsigned)std::min<long long>(4096, (n + 255) / 256), (unsigned)tables),
+                           dim3(256), 0, s, fcT, fcM, H, N, C);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_fc_mixed, dim3((unsigned)std::min<long long>(4096, (n + 255) / 256)), dim3(256), 0, s, fcT, fcM,
                        H, N, C);
     return hipGetLastError();

@@ -30,16 +30,20 @@ hipError_t bwd_pass_a(int N, const admm::BwdArgs& a, bool iso, bool lastk, bool 
 hipError_t bwd_iso_q(int N, const admm::BwdIsoArgs& a, bool lastk, hipStream_t s);
 // the column pass of P planes from `in` into `out`: the same buffer (in place), or -- the training forward with
 // a PSF gradient, whose r_k stay in the history -- another one
-hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH, int N, long long P, hipStream_t s);
+// bank: a PSF bank's table index (fcM then holds bank->T tables; in place only), null for one PSF
+hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH, int N, long long P, hipStream_t s,
+                  const admm::BankIdx* bank = nullptr);
 // PSF gradient: part[g][kx][ky] = scale * sum over plane group g (ppg planes) of conj(colFFT U_p) colFFT V_p,
 // kx in [0, N] (k_xspec's layout: k_xspec_reduce and k_psf_grad follow)
 hipError_t xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N, long long P, int ppg, float scale,
                  hipStream_t s);
 // fcM: [H][N + 1] then the column-block-packed copy [N / C][H][C] (C = pass_b_cols): H (2N + 1) floats
-hipError_t fc_mixed(const float* fcT, float* fcM, int H, int N, hipStream_t s);
+// (tables > 0: a PSF bank's tables, one after another in fcT and in fcM, in one launch)
+hipError_t fc_mixed(const float* fcT, float* fcM, int H, int N, hipStream_t s, int tables = 0);
 // b = H_t(xin) on the mixed transforms: the column pass with the complex PSF multiplier mM ([H][N + 1],
 // mt_mixed of the generic path's mT [N + 1][H], halved for the packed row transforms)
-hipError_t pass_b_cm(int H, cf* spec, const cf* mM, const cf* twH, int N, long long P, hipStream_t s);
-hipError_t mt_mixed(const cf* mT, cf* mM, int H, int N, hipStream_t s);
+hipError_t pass_b_cm(int H, cf* spec, const cf* mM, const cf* twH, int N, long long P, hipStream_t s,
+                     const admm::BankIdx* bank = nullptr);
+hipError_t mt_mixed(const cf* mT, cf* mM, int H, int N, hipStream_t s, int tables = 0);
 
 }  // namespace admm_mixed

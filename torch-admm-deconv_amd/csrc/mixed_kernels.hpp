@@ -549,7 +549,7 @@ __global__ void __launch_bounds__(256) k_row_c2r_m(const cf* __restrict__ spec, 
 // the packed row transforms' 1/(2HW), exactly), followed by the column-block-packed copy
 // fcP[cb][ky][c] = fcM[ky][cb C + c] (kx < N): a block's factors are one contiguous C H run, so a wave
 // reads whole lines and no line is shared with the neighbouring column blocks (which may run on other XCDs)
-static __global__ void k_fc_mixed(const float* __restrict__ fcT, float* __restrict__ fcM, int H, int N, int C) {
+__device__ __forceinline__ void fc_mixed_body(const float* __restrict__ fcT, float* __restrict__ fcM, int H, int N, int C) {
     const long long n = (long long)H * (N + 1), np = (long long)H * N;
     float* fcP = fcM + n;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n + np; i += (long long)gridDim.x * blockDim.x) {
@@ -563,16 +563,22 @@ static __global__ void k_fc_mixed(const float* __restrict__ fcT, float* __restri
         }
     }
 }
+static __global__ void k_fc_mixed(const float* __restrict__ fcT, float* __restrict__ fcM, int H, int N, int C) {
+    fc_mixed_body(fcT, fcM, H, N, C);
+}
 
 // the PSF multiplier for the mixed column pass: mM[ky][kx] = mT[kx][ky] / 2 (kx in [0, N]; the / 2 as for
 // k_fc_mixed)
-static __global__ void k_mt_mixed(const cf* __restrict__ mT, cf* __restrict__ mM, int H, int N) {
+__device__ __forceinline__ void mt_mixed_body(const cf* __restrict__ mT, cf* __restrict__ mM, int H, int N) {
     const long long n = (long long)H * (N + 1);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int ky = (int)(i / (N + 1)), kx = (int)(i % (N + 1));
         const cf v = mT[(size_t)kx * H + ky];
         mM[i] = mkc(0.5f * v.x, 0.5f * v.y);
     }
+}
+static __global__ void k_mt_mixed(const cf* __restrict__ mT, cf* __restrict__ mM, int H, int N) {
+    mt_mixed_body(mT, mM, H, N);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -590,10 +596,15 @@ static __global__ void k_mt_mixed(const cf* __restrict__ mT, cf* __restrict__ mM
 // reads r_k from the history, which the backward reads again, and writes x^ to the spectrum buffer); the
 // arithmetic is the in-place instance's.  A template parameter, so the in-place instances keep one buffer
 // resource and their code.
-template <int H, int CC, bool CM = false, bool OOP = false>
+// BK = BankIdx (one trailing argument; admm_kernels.hpp): a PSF bank -- the block's plane picks its table of
+// fcM (row-major and column-block-packed copies, H (2N + 1) floats per table) or of mM (CM, H (N + 1) values per
+// table).  A template parameter, like OOP; with the empty pack the kernel has the signature and the code it has
+// without the parameter.
+template <int H, int CC, bool CM = false, bool OOP = false, class... BK>
 __global__ void __launch_bounds__((MColG<H, CC>::NT))
 k_pass_b_m(cf* spec, const float* __restrict__ fcM, const cf* __restrict__ twH_g, int N, int colblocks, int order,
-           int fpack, const cf* __restrict__ mM = nullptr, cf* out = nullptr) {
+           int fpack, const cf* __restrict__ mM = nullptr, cf* out = nullptr, BK... bk) {
+    constexpr bool BANK = sizeof...(BK) > 0;
     using G = MColG<H, CC>;
     constexpr int Lc = G::Lc, Ec = G::Ec, C = G::C, EM = G::EM, NBz = G::NBz, Qz = G::Qz;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -605,6 +616,11 @@ k_pass_b_m(cf* spec, const float* __restrict__ fcM, const cf* __restrict__ twH_g
     int p, cb;
     pb_tile(xcd_remap(blockIdx.x, gridDim.x), colblocks, order, true, p, cb);
     const int col = cb * C + c;
+    if constexpr (BANK) {  // this plane's table
+        const size_t tb = (size_t)bank_tab(p, bk...);
+        if constexpr (CM) mM += tb * H * (N + 1);
+        else fcM += tb * H * (2 * N + 1);
+    }
     const rsrc_t rs = make_rsrc(spec + (size_t)p * H * N, (unsigned)((size_t)H * N * sizeof(cf)));
     const rsrc_t ro = OOP ? make_rsrc(out + (size_t)p * H * N, (unsigned)((size_t)H * N * sizeof(cf))) : rs;
     const int voff = (t * N + col) * (int)sizeof(cf);
@@ -684,6 +700,16 @@ k_pass_b_m(cf* spec, const float* __restrict__ fcM, const cf* __restrict__ twH_g
     mfft<H, Lc, EM, +1, 1, 1>(v, buf, tw, t, typename MCol<H>::Inv{});
 #pragma unroll
     for (int j = 0; j < Ec; ++j) bstore_cf(ro, voff, j * sstep, v[j]);
+}
+
+// a bank's tables: table blockIdx.y of fcT / fcM, of mT / mM
+static __global__ void k_fc_mixed_bank(const float* __restrict__ fcT, float* __restrict__ fcM, int H, int N, int C) {
+    const long long n = (long long)H * (N + 1), np = (long long)H * N;
+    fc_mixed_body(fcT + (size_t)blockIdx.y * n, fcM + (size_t)blockIdx.y * (n + np), H, N, C);
+}
+static __global__ void k_mt_mixed_bank(const cf* __restrict__ mT, cf* __restrict__ mM, int H, int N) {
+    const long long n = (long long)H * (N + 1);
+    mt_mixed_body(mT + (size_t)blockIdx.y * n, mM + (size_t)blockIdx.y * n, H, N);
 }
 
 // ---------------------------------------------------------------------------------------------
