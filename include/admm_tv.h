@@ -110,13 +110,31 @@ typedef struct admm_tv_desc {
  *    three-launch iteration everywhere else -- the odd row lengths (admm_tv_supported == 4, either
  *    orientation) included, as for stateful solves; admm_tv_path reports ADMM_TV_PATH_GENERIC there.
  *  - Refused, by the size queries and admm_tv_path as by the calls: kh == 0 (ADMM_TV_EINVAL); groups > 1, an
- *    all-reduce hook, ADMM_TV_FLAG_F64 (every *_f64 entry point), ADMM_TV_FLAG_PSF_GRAD, more than 65,535
- *    PSFs, and the training entry points (admm_tv_forward_train, admm_tv_backward, admm_tv_history_size,
- *    admm_tv_backward_workspace_size): ADMM_TV_EUNSUPPORTED.  Training with a bank is the next step and is
- *    not implemented: a bank is inference only. */
+ *    all-reduce hook, ADMM_TV_FLAG_F64 (every *_f64 entry point), more than 65,535 PSFs: ADMM_TV_EUNSUPPORTED.
+ *  - Training is opt-in, ADMM_TV_FLAG_PSF_BANK_TRAIN.  Without that bit a bank is inference only:
+ *    ADMM_TV_FLAG_PSF_GRAD and the training entry points (admm_tv_forward_train, admm_tv_backward,
+ *    admm_tv_history_size, admm_tv_backward_workspace_size, admm_tv_path(desc, 1)) answer ADMM_TV_EUNSUPPORTED,
+ *    as every library of this ABI version does, so bank | ADMM_TV_FLAG_PSF_BANK_TRAIN on a training call
+ *    probes for the feature.
+ *  - With a bank bit and ADMM_TV_FLAG_PSF_BANK_TRAIN: admm_tv_history_size (the history is per plane: the
+ *    shared-PSF descriptor's), admm_tv_forward_train, admm_tv_backward_workspace_size, admm_tv_backward and
+ *    admm_tv_path(desc, 1) accept the descriptor, with or without ADMM_TV_FLAG_PSF_GRAD; admm_tv_workspace_size,
+ *    admm_tv_forward, admm_tv_psf_transpose and admm_tv_path(desc, 0) answer as without the bit (with
+ *    ADMM_TV_FLAG_PSF_GRAD the workspace also holds T sigma tables).  gxin is per plane, glam and grho stay one
+ *    value each (lambda and rho are the bank's); with ADMM_TV_FLAG_PSF_GRAD gkern holds T * kh * kw floats in
+ *    bank order ((Bk, Ck, kh, kw) contiguous), table t's gradient summed over the planes that use it, and xin
+ *    is required; maxit == 0 zeroes all of them.  The backward workspace then holds, per table, a real fp64
+ *    and a complex fp64 accumulator over the half spectrum (24 bytes per point and table), the cross-spectrum
+ *    partials of its plane chunks and kh complex fp64 rows of W/2 + 1 points.  Paths are those of inference:
+ *    fused, fused mixed-radix, generic at every other size.
+ *  - The bit without a bank bit is ADMM_TV_EINVAL everywhere; on admm_tv_forward_state,
+ *    admm_tv_state_workspace_size and admm_tv_path(desc, 2) it is ADMM_TV_EINVAL like ADMM_TV_FLAG_PSF_GRAD.
+ *    With the bit, fp64, groups > 1, a hook, kh == 0 and more than 65,535 PSFs stay refused as above: fp64
+ *    banks, grouped or sharded bank training and a backward from a solver state are not implemented. */
 #define ADMM_TV_FLAG_PSF_PER_IMAGE 4   /* kern holds B  PSFs: image b uses PSF b            */
 #define ADMM_TV_FLAG_PSF_PER_CHANNEL 8 /* kern holds C  PSFs: channel c uses PSF c          */
 /* both: kern holds B*C PSFs, plane (b, c) uses PSF b*C + c                                  */
+#define ADMM_TV_FLAG_PSF_BANK_TRAIN 16 /* with a bank bit: the training entry points take the bank */
 
 /* ABI version (ADMM_TV_ABI_VERSION). */
 int admm_tv_abi_version(void);

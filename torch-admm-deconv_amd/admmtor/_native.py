@@ -97,6 +97,8 @@ ADMM_TV_FLAG_F64 = 2  # fp64 solve: the *_f64 entry points, double arrays
 # a PSF bank: kern holds (Bk, Ck, k, k) PSFs, plane (b, c) uses PSF (Bk > 1 ? b : 0) * Ck + (Ck > 1 ? c : 0)
 ADMM_TV_FLAG_PSF_PER_IMAGE = 4    # Bk = B
 ADMM_TV_FLAG_PSF_PER_CHANNEL = 8  # Ck = C
+# with a bank bit: the training entry points take the bank (without it a bank is inference only)
+ADMM_TV_FLAG_PSF_BANK_TRAIN = 16
 ABI_VERSION = 7
 # admm_tv_path codes (include/admm_tv.h)
 PATHS = {1: "fused", 2: "generic", 3: "fused mixed-radix", 4: "fused odd-length"}

@@ -18,6 +18,13 @@ graph, with no graph break, and the autograd formula is registered on the op its
                             need_x, need_s, need_k) -> (gx, glam, grho, gkern)
       admm_tv_backward; gradients that are not needed come back as empty tensors
 
+  admm_hip::fft_admm_tv_bank_fwd_train(x, lam, rho, kerns, iso, maxit, psf_grad) -> (out, hist)
+  admm_hip::fft_admm_tv_bank_bwd(gout, x, lam, rho, kerns, hist, iso, maxit, psf_grad,
+                                 need_x, need_s, need_k) -> (gx, glam, grho, gkerns)
+      the same pair for a PSF bank (Bk, Ck, k, k) (ADMM_TV_FLAG_PSF_BANK_TRAIN): fp32, one module; gkerns is
+      shaped like kerns, each PSF's gradient summed over the planes that use it.  First order only: the
+      backward op's autograd formula raises
+
 All tensor arguments share one dtype -- fp32, or fp64 for an fp64 solve (ADMM_TV_FLAG_F64: the
 reference computes in xin.dtype, so fp64 inputs get fp64 arithmetic) -- and are contiguous, on one
 ROCm device (the public wrapper in ``admmtor.eops.deconv`` stages host / half inputs).  The backward op
@@ -36,7 +43,8 @@ from torch import Tensor
 
 from . import _native
 
-__all__ = ["fft_admm_tv_fwd", "fft_admm_tv_state", "fft_admm_tv_fwd_train", "fft_admm_tv_bwd"]
+__all__ = ["fft_admm_tv_fwd", "fft_admm_tv_state", "fft_admm_tv_fwd_train", "fft_admm_tv_bwd",
+           "fft_admm_tv_bank_fwd_train", "fft_admm_tv_bank_bwd"]
 
 
 def _k(kern: Tensor) -> int:
@@ -299,3 +307,123 @@ def _bwd_backward(ctx, ggx, ggl, ggr, ggk):
 
 
 torch.library.register_autograd("admm_hip::fft_admm_tv_bwd", _bwd_backward, setup_context=_bwd_setup_context)
+
+
+# ---------------------------------------------------------------- training with a PSF bank
+def _bank_train_flags(x: Tensor, kerns: Tensor, psf_grad: bool) -> int:
+    """The descriptor flags of a bank training call: the bank's bits with ADMM_TV_FLAG_PSF_BANK_TRAIN (a
+    (1, 1, k, k) bank sets neither: the shared-PSF descriptor), and the PSF-gradient bit."""
+    bank = _bank(x, kerns)
+    return (bank | _native.ADMM_TV_FLAG_PSF_BANK_TRAIN if bank else 0) | \
+        (_native.ADMM_TV_FLAG_PSF_GRAD if psf_grad else 0)
+
+
+def _check_bank_op(who: str, x: Tensor, lam: Tensor, kerns: Tensor) -> None:
+    if x.dtype != torch.float32 or lam.numel() != 1:
+        raise NotImplementedError(f"admm_hip::{who}: fp32, one module (lam, rho of one element)")
+    if kerns.dim() != 4 or kerns.numel() == 0:
+        raise ValueError(f"admm_hip::{who}: kerns is a PSF bank (Bk, Ck, k, k)")
+
+
+@torch.library.custom_op("admm_hip::fft_admm_tv_bank_fwd_train", mutates_args=())
+def fft_admm_tv_bank_fwd_train(x: Tensor, lam: Tensor, rho: Tensor, kerns: Tensor, iso: bool, maxit: int,
+                               psf_grad: bool) -> Tuple[Tensor, Tensor]:
+    """admm_tv_forward_train with a PSF bank: the solve plus the history its backward reads (per plane, as
+    for one PSF; with psf_grad the r_k spectra)."""
+    _check_device(x, lam, rho, kerns)
+    _check_bank_op("fft_admm_tv_bank_fwd_train", x, lam, kerns)
+    B, C, H, W = x.shape
+    _check_supported(H, W, False)
+    d = _desc(x, lam, kerns, iso, maxit, _bank_train_flags(x, kerns, psf_grad))
+    x, lam, rho, kerns = x.contiguous(), lam.contiguous(), rho.contiguous(), kerns.contiguous()
+    ws = torch.empty(_native.workspace_size(d), dtype=torch.uint8, device=x.device)
+    hist = torch.empty(max(_native.history_size(d), 1), dtype=torch.uint8, device=x.device)
+    out = torch.empty((B, C, H, W), dtype=x.dtype, device=x.device)
+    _native.check(_native.load().admm_tv_forward_train(
+        d, x.data_ptr(), kerns.data_ptr(), lam.data_ptr(), rho.data_ptr(), out.data_ptr(), hist.data_ptr(),
+        hist.numel(), ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return out, hist
+
+
+@fft_admm_tv_bank_fwd_train.register_fake
+def _(x, lam, rho, kerns, iso, maxit, psf_grad):
+    B, C, H, W = x.shape
+    out = x.new_empty((B, C, H, W), dtype=x.dtype)
+    k = kerns.shape[-1]
+    if _is_concrete(B, C, H, W, k):  # the history is per plane: the shared-PSF descriptor's size
+        n = max(_native.history_size(_native.desc(B, C, H, W, k, iso, maxit,
+                                                  _native.ADMM_TV_FLAG_PSF_GRAD if psf_grad else 0)), 1)
+    else:
+        n = torch.library.get_ctx().new_dynamic_size()
+    return out, x.new_empty((n,), dtype=torch.uint8)
+
+
+@torch.library.custom_op("admm_hip::fft_admm_tv_bank_bwd", mutates_args=())
+def fft_admm_tv_bank_bwd(gout: Tensor, x: Tensor, lam: Tensor, rho: Tensor, kerns: Tensor, hist: Tensor, iso: bool,
+                         maxit: int, psf_grad: bool, need_x: bool, need_s: bool,
+                         need_k: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """admm_tv_backward with a PSF bank: (dL/dx, dL/dlam, dL/drho, dL/dkerns) from dL/dout and the history;
+    dL/dkerns is shaped like kerns.  Gradients that are not needed come back as empty tensors."""
+    _check_device(gout, x, lam, rho, kerns, hist)
+    _check_bank_op("fft_admm_tv_bank_bwd", gout, lam, kerns)
+    B, C, H, W = gout.shape
+    if need_k and not psf_grad:
+        raise RuntimeError("admmtor: PSF gradient requested but the forward did not keep the spectra")
+    if psf_grad and tuple(x.shape) != (B, C, H, W):
+        raise RuntimeError("admm_hip::fft_admm_tv_bank_bwd: the PSF gradient needs the forward's input x")
+    d = _native.desc(B, C, H, W, _k(kerns), iso, maxit, _bank_train_flags(gout, kerns, psf_grad))
+    dev, dt = gout.device, torch.float32
+    g = gout.contiguous()
+    e = torch.empty(0, dtype=dt, device=dev)
+    gx = torch.empty((B, C, H, W), dtype=dt, device=dev) if need_x else e
+    gl = torch.empty(1, dtype=dt, device=dev) if need_s else e.clone()
+    gr = torch.empty(1, dtype=dt, device=dev) if need_s else e.clone()
+    gk = torch.empty(tuple(kerns.shape), dtype=dt, device=dev) if need_k else e.clone()
+    ws = torch.empty(_native.backward_workspace_size(d), dtype=torch.uint8, device=dev)
+    xc = x.contiguous() if psf_grad else None
+    _native.check(_native.load().admm_tv_backward(
+        d, xc.data_ptr() if psf_grad else None, kerns.contiguous().data_ptr(), lam.contiguous().data_ptr(),
+        rho.contiguous().data_ptr(), g.data_ptr(), hist.data_ptr(), hist.numel(),
+        gx.data_ptr() if need_x else None, gl.data_ptr() if need_s else None, gr.data_ptr() if need_s else None,
+        gk.data_ptr() if need_k else None, ws.data_ptr(), ws.numel(), _stream(dev)))
+    return gx, gl, gr, gk
+
+
+@fft_admm_tv_bank_bwd.register_fake
+def _(gout, x, lam, rho, kerns, hist, iso, maxit, psf_grad, need_x, need_s, need_k):
+    B, C, H, W = gout.shape
+
+    def mk(shape):
+        return gout.new_empty(shape, dtype=lam.dtype)
+    return (mk((B, C, H, W)) if need_x else mk((0,)), mk((1,)) if need_s else mk((0,)),
+            mk((1,)) if need_s else mk((0,)), mk(tuple(kerns.shape)) if need_k else mk((0,)))
+
+
+def _bank_backward(ctx, gout, ghist):
+    if gout is None:
+        return (None,) * 7
+    x, lam, rho, kerns, hist = ctx.saved_tensors
+    if ctx.xref is not None and ctx.xref[0]._version == ctx.xref[1]:
+        x = ctx.xref[0]
+    need_x = ctx.needs_input_grad[0]
+    need_s = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+    need_k = ctx.needs_input_grad[3]
+    gx, gl, gr, gk = torch.ops.admm_hip.fft_admm_tv_bank_bwd(
+        gout, x, lam, rho, kerns, hist, ctx.iso, ctx.maxit, ctx.psf_grad, need_x, need_s, need_k)
+    return (gx if need_x else None,
+            gl if ctx.needs_input_grad[1] else None,
+            gr if ctx.needs_input_grad[2] else None,
+            gk if need_k else None, None, None, None)
+
+
+# (the context is the shared op's: grads not materialised, the private copy of x for the PSF gradient)
+torch.library.register_autograd("admm_hip::fft_admm_tv_bank_fwd_train", _bank_backward, setup_context=_setup_context)
+
+
+def _bank_bwd_backward(ctx, *grads):
+    raise NotImplementedError("admm_hip::fft_admm_tv_bank_bwd: a double backward through a PSF bank is not "
+                              "implemented (create_graph=True); fft_admm_tv with one PSF has one")
+
+
+torch.library.register_autograd("admm_hip::fft_admm_tv_bank_bwd", _bank_bwd_backward,
+                                setup_context=lambda ctx, inputs, output: None)

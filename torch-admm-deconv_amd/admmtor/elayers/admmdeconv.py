@@ -11,9 +11,9 @@ from typing import Callable, Tuple
 
 import torch
 
-from admmtor.eops.deconv import fft_admm_tv, identity
+from admmtor.eops.deconv import fft_admm_tv, fft_admm_tv_bank_train, identity
 
-__all__ = ["ADMMDeconv"]
+__all__ = ["ADMMDeconv", "ADMMDeconvBank"]
 
 
 class ADMMDeconv(torch.nn.Module):
@@ -75,3 +75,38 @@ class ADMMDeconv(torch.nn.Module):
     def extra_repr(self) -> str:
         k = tuple(self.w.shape[-2:]) if self.w.numel() else ()
         return f"kern_size={k}, max_iters={self.max_iters}, iso={self.iso}"
+
+
+class ADMMDeconvBank(ADMMDeconv):
+    """:class:`ADMMDeconv` with a learnable PSF per channel (optics whose blur differs between R, G and B).
+
+    ``w`` is a PSF bank ``(1, channels, kh, kw)``; every channel's slice is initialised as ``ADMMDeconv``
+    initialises its one PSF (xavier-uniform on a ``(1, 1, kh, kw)`` tensor, channel after channel, so channel 0
+    of a seeded init is ``ADMMDeconv``'s ``w``).  Parameter / buffer names and registration order are
+    ``ADMMDeconv``'s; ``forward`` is one native training step through ``fft_admm_tv_bank_train``.  A bank needs
+    a PSF: an empty ``kern_size`` raises ``ValueError``.
+    """
+
+    def __init__(self, kern_size: Tuple[int, int], max_iters: int, channels: int, lmbda: float = None,
+                 rho: float = None, iso: bool = True, bias: bool = False, activation: Callable = identity):
+        if not kern_size:
+            raise ValueError("ADMMDeconvBank needs a PSF size (kh, kw); ADMMDeconv is the layer without a PSF")
+        if int(channels) < 1:
+            raise ValueError("ADMMDeconvBank: channels must be at least 1")
+        self.channels = int(channels)
+        super().__init__(kern_size, max_iters, lmbda, rho, iso, bias, activation)
+
+    def _make_psf(self, kern_size):
+        self.w = torch.nn.Parameter(torch.empty((1, self.channels, *kern_size)), requires_grad=True)
+        with torch.no_grad():
+            for c in range(self.channels):
+                one = torch.empty((1, 1, *kern_size))
+                torch.nn.init.xavier_uniform_(one)
+                self.w[0, c] = one[0, 0]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.activation(
+            fft_admm_tv_bank_train(x, self.lmbda, self.rho, self.w, self.iso, self.max_iters) + self.b)
+
+    def extra_repr(self) -> str:
+        return f"channels={self.channels}, " + super().extra_repr()

@@ -39,6 +39,7 @@ __all__ = [
     "fft_admm_tv_until",
     "fft_admm_tv_bank",
     "fft_admm_tv_bank_state",
+    "fft_admm_tv_bank_train",
 ]
 
 
@@ -349,8 +350,8 @@ def fft_admm_tv_bank_state(xin: torch.Tensor, lmbd, rho, kerns: torch.Tensor, is
     _check_bank(xin, kerns, "fft_admm_tv_bank_state")
     if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad
                                        for v in (xin, lmbd, rho, kerns, *(state or ()))):
-        raise RuntimeError("a PSF bank is inference only: an input requires grad (training with a bank is not "
-                           "implemented; run under torch.no_grad())")
+        raise RuntimeError("this PSF-bank call is inference only: an input requires grad (fft_admm_tv_bank_train is "
+                           "the differentiable call; or run under torch.no_grad())")
     home = xin.device
     maxit = max(0, int(maxit))
     xin, lmbd, rho, kerns = _stage(xin, lmbd, rho, kerns)
@@ -381,8 +382,8 @@ def fft_admm_tv_bank(xin: torch.Tensor, lmbd, rho, kerns: torch.Tensor, iso: boo
     _check_bank(xin, kerns, "fft_admm_tv_bank")
     if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad
                                        for v in (xin, lmbd, rho, kerns)):
-        raise RuntimeError("a PSF bank is inference only: an input requires grad (training with a bank is not "
-                           "implemented; run under torch.no_grad())")
+        raise RuntimeError("this PSF-bank call is inference only: an input requires grad (fft_admm_tv_bank_train is "
+                           "the differentiable call; or run under torch.no_grad())")
     home = xin.device
     maxit = max(0, int(maxit))
     if xin.numel() == 0:
@@ -394,6 +395,41 @@ def fft_admm_tv_bank(xin: torch.Tensor, lmbd, rho, kerns: torch.Tensor, iso: boo
         kc = kerns.detach().to(device=dev, dtype=torch.float32).contiguous()
         out = torch.ops.admm_hip.fft_admm_tv_fwd(xc, _as_device_scalar(lmbd, dev), _as_device_scalar(rho, dev), kc,
                                                  bool(iso), maxit)
+    return out.to(device=home)
+
+
+def fft_admm_tv_bank_train(xin: torch.Tensor, lmbd, rho, kerns: torch.Tensor, iso: bool = False,
+                           maxit: int = 100) -> torch.Tensor:
+    """:func:`fft_admm_tv_bank`, differentiable in ``xin``, ``lmbd``, ``rho`` and ``kerns``: blind deconvolution
+    of a batch (a learnable PSF per image), optics calibration (one per colour channel), a network that emits
+    a PSF per image upstream of the solve.
+
+    ``kerns`` is a bank ``(Bk, Ck, k, k)`` as in :func:`fft_admm_tv_bank_state`.  Its gradient has its shape:
+    each PSF's is summed over the planes that use it; ``lmbd`` and ``rho`` are shared, so theirs stay one value
+    each.  One native training step over all ``B C`` planes -- for ``iso=True`` with the norm over batch and
+    channel, which a loop of single-image training calls would not differentiate.  When gradients are off or
+    no input requires grad this is :func:`fft_admm_tv_bank` bit for bit; a ``(1, 1, k, k)`` bank is
+    :func:`fft_admm_tv` bit for bit, gradients included.  The r_k spectra the PSF gradient needs are kept only
+    when ``kerns`` requires grad.  First order: ``create_graph=True`` raises ``NotImplementedError``.
+    Validation and errors as :func:`fft_admm_tv_bank` (fp32 only; host inputs are staged to the current ROCm
+    device, gradients flow back through the copies)."""
+    if not isinstance(kerns, torch.Tensor):
+        kerns = torch.as_tensor(kerns)
+    _check_bank(xin, kerns, "fft_admm_tv_bank_train")
+    needs_grad = torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad
+                                                 for v in (xin, lmbd, rho, kerns))
+    if not needs_grad:
+        return fft_admm_tv_bank(xin, lmbd, rho, kerns, iso, maxit)
+    home = xin.device
+    maxit = max(0, int(maxit))
+    if xin.numel() == 0:
+        return torch.zeros(xin.shape, dtype=torch.float32, device=home)
+    xin, lmbd, rho, kerns = _stage(xin, lmbd, rho, kerns)
+    dev = xin.device
+    xc = xin.to(torch.float32).contiguous()  # differentiable cast (autocast half inputs)
+    kc = kerns.to(device=dev, dtype=torch.float32).contiguous()
+    out, _ = torch.ops.admm_hip.fft_admm_tv_bank_fwd_train(
+        xc, _scalar_input(lmbd, dev), _scalar_input(rho, dev), kc, bool(iso), maxit, bool(kerns.requires_grad))
     return out.to(device=home)
 
 

@@ -533,10 +533,26 @@ namespace admm {
 // k_xspec forms sum_p conj(colFFT(U_p)) colFFT(V_p) per frequency from two sets of row
 // spectra, plane-group partials, with the packed column 0 split into kx = 0 and kx = N.
 // ---------------------------------------------------------------------------
-template <int H, int C, bool COL0>
+// plane group grp's planes, for the cross-spectrum kernels: without a bank the planes [grp ppg, (grp + 1) ppg) of
+// P; with one (XBank) the loop runs over the table's plane numbers j and xplane maps j to the solve's plane
+__device__ __forceinline__ int xplanes_begin(int grp, int ppg) { return grp * ppg; }
+__device__ __forceinline__ int xplanes_end(int grp, int ppg, int P) { return min(P, (grp + 1) * ppg); }
+__device__ __forceinline__ size_t xplane(int, int p) { return (size_t)p; }
+__device__ __forceinline__ int xplanes_begin(int grp, int ppg, const XBank& b) { return (grp % b.cpt) * ppg; }
+__device__ __forceinline__ int xplanes_end(int grp, int ppg, int, const XBank& b) {
+    return min(b.n, (grp % b.cpt + 1) * ppg);
+}
+__device__ __forceinline__ size_t xplane(int grp, int j, const XBank& b) {
+    return (size_t)(grp / b.cpt) * b.tb + (size_t)j * b.stride;
+}
+
+// XB = XBank (one trailing argument): a PSF bank's gradient -- plane group grp is a chunk of ONE table's planes
+// (admm_kernels.hpp XBank), so the partials can be reduced per table.  An empty pack is the shared-PSF kernel:
+// the bank's terms are compile-time branches.
+template <int H, int C, bool COL0, class... XB>
 __global__ void __launch_bounds__(C * (H / RowCfg<H>::E), 1)
     k_xspec(const cf* __restrict__ U, const cf* __restrict__ V, cf* __restrict__ part, const cf* __restrict__ twH_g,
-            int N, int colblocks, int P, int ppg) {
+            int N, int colblocks, int P, int ppg, XB... xb) {
     using G = ColGeom<H, C>;
     constexpr int E = G::E, L = G::L;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -558,10 +574,10 @@ __global__ void __launch_bounds__(C * (H / RowCfg<H>::E), 1)
         for (int j = 0; j < E; ++j) accn[j] = mkc(0.f, 0.f);
     }
     __syncthreads();
-    const int p1 = min(P, (grp + 1) * ppg);
-    for (int p = grp * ppg; p < p1; ++p) {
-        const cf* up = U + (size_t)p * H * N + col;
-        const cf* vp = V + (size_t)p * H * N + col;
+    const int p1 = xplanes_end(grp, ppg, P, xb...);
+    for (int p = xplanes_begin(grp, ppg, xb...); p < p1; ++p) {
+        const cf* up = U + xplane(grp, p, xb...) * H * N + col;
+        const cf* vp = V + xplane(grp, p, xb...) * H * N + col;
         cf u[E], v[E];
 #pragma unroll
         for (int j = 0; j < E; ++j) u[j] = up[(size_t)(t + L * j) * N];
@@ -678,6 +694,122 @@ __global__ void k_psf_grad(const double2* __restrict__ A, const double2* __restr
         __syncthreads();
     }
     if (threadIdx.x == 0) gk[tap] = (T)red[0];
+}
+
+// ---------------------------------------------------------------------------
+// PSF gradient of a bank (training with ADMM_TV_FLAG_PSF_BANK_TRAIN): one (A_t, Z_t, sigma_t) per table t,
+//   A_t(f) = sum_k fc_t(f)^2 Re sum_{p in P_t} conj(X^_{k,p}(f)) R_{k,p}(f),  Z_t(f) = sum_{p in P_t} conj(Bbar_p(f)) Xin_p(f)
+// from the cross-spectrum kernels' per-table plane groups (XBank).  A keeps its real part only (fp64, summed over
+// the iterations), Z exists once at the end: T (N + 1) H (8 + 16) bytes.
+// ---------------------------------------------------------------------------
+// table blockIdx.y: its cpt partials summed in a fixed order, in fp64.  fcT (T tables): A_t += fc_t^2 Re(sum);
+// null: Z_t = sum.
+static __global__ void k_xspec_reduce_bank(const cf* __restrict__ part, int cpt, long long nf, const float* __restrict__ fcT,
+                                           double* __restrict__ accA, double2* __restrict__ accZ) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nf) return;
+    const size_t to = (size_t)blockIdx.y * nf;
+    const cf* pt = part + to * cpt;
+    double re = 0.0, im = 0.0;
+    for (int g = 0; g < cpt; ++g) {
+        const cf v = pt[(size_t)g * nf + i];
+        re += v.x;
+        im += v.y;
+    }
+    if (fcT) {
+        const double f = fcT[to + i];
+        accA[to + i] += f * f * re;
+    } else {
+        accZ[to + i] = make_double2(re, im);
+    }
+}
+
+// The bank's taps, separably.  k_psf_grad sums every tap directly over the half plane with two sincospi per
+// point -- T k^2 (N + 1) H of them for a bank.  Both of its terms share the phase of tap (a, b) once Z carries
+// the anchor's shift:
+//   Q_t(f)      = -2 HW c(kx) A_t(f) conj(sigma_t(f)) + (c(kx) zscale / HW) Z_t(f) e^{+2 pi i c (ky/H + kx/W)}
+//   S_t[a][kx]  = sum_ky Eh[a][ky] Q_t(kx, ky),      Eh[a][ky] = e^{-2 pi i a ky / H}      (stage 1)
+//   gk_t[a][b]  = Re sum_kx Ew[b][kx] S_t[a][kx],    Ew[b][kx] = e^{-2 pi i b kx / W}      (stage 2)
+// ~ T k (N + 1) H complex fp64 multiply-adds, the phases from two tables built once (the anchor c = k / 2 < k is
+// a row of each).  Every sum is fp64 in a fixed order (a thread's strided terms, then an LDS tree).
+static __global__ void k_tap_tables(double2* __restrict__ Eh, double2* __restrict__ Ew, int k, int H, int W) {
+    const int N1 = W / 2 + 1;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long nh = (long long)k * H, nw = (long long)k * N1;
+    double s, c;
+    if (i < nh) {
+        const int a = (int)(i / H), ky = (int)(i % H);
+        sincospi(2.0 * (double)(((long long)a * ky) % H) / H, &s, &c);
+        Eh[i] = make_double2(c, -s);
+    } else if (i < nh + nw) {
+        const long long j = i - nh;
+        const int b = (int)(j / N1), kx = (int)(j % N1);
+        sincospi(2.0 * (double)(((long long)b * kx) % W) / W, &s, &c);
+        Ew[j] = make_double2(c, -s);
+    }
+}
+
+// stage 1: block (kx, t).  A thread forms Q at its ky = tid, tid + 256, ... once (A, Z and sigma are read once,
+// coalesced along ky: the tables are [kx][ky]) and parks it over Z, which nothing reads afterwards; the k sums
+// over ky then re-read only what the same thread wrote (no barrier between), against Eh's row a.
+static __global__ void __launch_bounds__(256)
+    k_psf_taps_col(const double* __restrict__ A, double2* Z, const double2* __restrict__ sigma,
+                   const double2* __restrict__ Eh, const double2* __restrict__ Ew, double2* __restrict__ S, int k, int H,
+                   int W, double zscale) {
+    __shared__ double red[2][256];
+    const int N1 = W / 2 + 1;
+    const int kx = blockIdx.x, c = k / 2;
+    const size_t to = (size_t)blockIdx.y * N1 * H + (size_t)kx * H;
+    const double HW = (double)H * W;
+    const double cw = (kx == 0 || 2 * kx == W) ? 1.0 : 2.0;  // self-conjugate columns once
+    const double q2 = -2.0 * HW * cw, q1 = cw / HW * zscale;
+    const double2 ewc = Ew[(size_t)c * N1 + kx];  // conj: e^{+2 pi i c kx / W}
+    for (int ky = threadIdx.x; ky < H; ky += blockDim.x) {
+        const double2 sg = sigma[to + ky], z = Z[to + ky], ehc = Eh[(size_t)c * H + ky];
+        const double a2 = q2 * A[to + ky];
+        // conj(ehc) conj(ewc)
+        const double pr = ehc.x * ewc.x - ehc.y * ewc.y, pi = -(ehc.x * ewc.y + ehc.y * ewc.x);
+        Z[to + ky] = make_double2(a2 * sg.x + q1 * (z.x * pr - z.y * pi), -a2 * sg.y + q1 * (z.x * pi + z.y * pr));
+    }
+    for (int a = 0; a < k; ++a) {
+        double re = 0.0, im = 0.0;
+        for (int ky = threadIdx.x; ky < H; ky += blockDim.x) {
+            const double2 q = Z[to + ky], e = Eh[(size_t)a * H + ky];
+            re += e.x * q.x - e.y * q.y;
+            im += e.x * q.y + e.y * q.x;
+        }
+        red[0][threadIdx.x] = re;
+        red[1][threadIdx.x] = im;
+        __syncthreads();
+        for (int o = blockDim.x / 2; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) {
+                red[0][threadIdx.x] += red[0][threadIdx.x + o];
+                red[1][threadIdx.x] += red[1][threadIdx.x + o];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) S[((size_t)blockIdx.y * k + a) * N1 + kx] = make_double2(red[0][0], red[1][0]);
+        __syncthreads();  // red is rewritten by the next a
+    }
+}
+
+// stage 2: block (tap, t): gk_t[a][b] = Re sum_kx Ew[b][kx] S_t[a][kx]
+static __global__ void __launch_bounds__(256)
+    k_psf_taps_row(const double2* __restrict__ S, const double2* __restrict__ Ew, int k, int W, float* __restrict__ gk) {
+    __shared__ double red[256];
+    const int N1 = W / 2 + 1;
+    const int a = blockIdx.x / k, b = blockIdx.x % k;
+    const double2* st = S + ((size_t)blockIdx.y * k + a) * N1;
+    const double2* ew = Ew + (size_t)b * N1;
+    double acc = 0.0;
+    for (int kx = threadIdx.x; kx < N1; kx += blockDim.x) acc += ew[kx].x * st[kx].x - ew[kx].y * st[kx].y;
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) gk[(size_t)blockIdx.y * k * k + blockIdx.x] = (float)red[0];
 }
 
 }  // namespace admm

@@ -165,6 +165,14 @@ BankIdx bank_of(const admm_tv_desc& d) {
 // planes in a row that share a table (the column pass's planes per block divide it)
 int bank_run(const admm_tv_desc& d) { return (d.flags & ADMM_TV_FLAG_PSF_PER_CHANNEL) ? 1 : (int)d.C; }
 constexpr long long kBankMax = 65535;  // the setup kernels take the table from a grid dimension
+// the bank's PSF gradient: table t's planes (XBank) in chunks of ppg -- a per-image bank's C consecutive planes, a
+// per-channel bank's B planes at stride C, a per-plane bank's one
+XBank xbank_of(const admm_tv_desc& d, int ppg) {
+    const bool pi = (d.flags & ADMM_TV_FLAG_PSF_PER_IMAGE) != 0, pc = (d.flags & ADMM_TV_FLAG_PSF_PER_CHANNEL) != 0;
+    const int n = pi && pc ? 1 : pi ? (int)d.C : (int)d.B;
+    ppg = std::max(ppg, 1);
+    return XBank{pi && !pc ? (int)d.C : 1, pi ? 1 : (int)d.C, n, (n + ppg - 1) / ppg};
+}
 
 constexpr size_t kAlign = 256;
 size_t up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
@@ -264,7 +272,7 @@ Layout make_layout(const admm_tv_desc& d) {
     L.fcM = L.mixed ? take(G * T * (2 * N + 1) * H * sizeof(float)) : 0;  // per module: [H][N + 1] + packed copy, k_fc_mixed
     L.mM = (L.mixed && k > 0) ? take(T * (N + 1) * H * 2 * sizeof(float)) : 0;
     L.spec2 = L.odd ? take(P * H * (size_t)L.ldw * csz) : 0;
-    L.sigma = (k > 0 && (d.flags & ADMM_TV_FLAG_PSF_GRAD)) ? take((N + 1) * H * sizeof(double2)) : 0;
+    L.sigma = (k > 0 && (d.flags & ADMM_TV_FLAG_PSF_GRAD)) ? take(T * (N + 1) * H * sizeof(double2)) : 0;  // per table
     if (d.iso) {
         // plane groups for the iso norm pass: enough (group,row) items to fill the chip
         // planes per group: at most 64 (each group writes and the reduce reads one 2HW partial;
@@ -544,7 +552,7 @@ template <int H, int C> int pass_b_hc(const cf* spec, cf* out, const float* fcT,
     // 5,624, C3 iso +0.5 %; profiles/r03_sweep_knobs_c3.txt); pair-interleaved remap (4, 5) +9 %
     // (profiles/r03_ab_passb_order.txt)
     const int pmode = env_int("ADMM_PASSB_PMODE", 2);
-    if (bank) {  // inference (mode 0) and H_t (mode 1)
+    if (bank) {  // the Wiener factor (mode 0), H_t (mode 1) and its adjoint (mode 2)
         if (mode == 0) {
             if (int e = set_lds(k_pass_b<H, C, 0, BankIdx>, G::lds_bytes())) return e;
             hipLaunchKernelGGL((k_pass_b<H, C, 0, BankIdx>), grid, dim3(G::NT), G::lds_bytes(), s, spec, out, fcT, mT, twH, N,
@@ -553,8 +561,10 @@ template <int H, int C> int pass_b_hc(const cf* spec, cf* out, const float* fcT,
             if (int e = set_lds(k_pass_b<H, C, 1, BankIdx>, G::lds_bytes())) return e;
             hipLaunchKernelGGL((k_pass_b<H, C, 1, BankIdx>), grid, dim3(G::NT), G::lds_bytes(), s, spec, out, fcT, mT, twH, N,
                                colblocks, ppm, order, fpack, gp, P, pmode, *bank);
-        } else {
-            return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: no adjoint column pass (inference only)");
+        } else {  // the training backward's x^_in = H_t^T b^: each plane's conjugate multiplier
+            if (int e = set_lds(k_pass_b<H, C, 2, BankIdx>, G::lds_bytes())) return e;
+            hipLaunchKernelGGL((k_pass_b<H, C, 2, BankIdx>), grid, dim3(G::NT), G::lds_bytes(), s, spec, out, fcT, mT, twH, N,
+                               colblocks, ppm, order, fpack, gp, P, pmode, *bank);
         }
         return launch_check("k_pass_b<bank>");
     }
@@ -620,10 +630,22 @@ int pass_b(int H, cf* spec, const float* fcT, const cf* mT, const cf* twH, int N
 }
 
 // cross-spectrum partials sum_{p in group} conj(colFFT U_p) colFFT V_p  -> part[g][N+1][H]
+// xb: a PSF bank's gradient -- T x xb->cpt plane groups, each a chunk of one table's planes (XBank)
 template <int H, int C> int xspec_hc(const cf* U, const cf* V, cf* part, const cf* twH, int N, int P, int ppg,
-                                     hipStream_t s) {
+                                     hipStream_t s, const XBank* xb, int T) {
     using G = ColGeom<H, C>;
     const int colblocks = N / C;
+    if (xb) {
+        const int groups = T * xb->cpt;
+        if (int e = set_lds(k_xspec<H, C, true, XBank>, G::lds_bytes())) return e;
+        if (int e = set_lds(k_xspec<H, C, false, XBank>, G::lds_bytes())) return e;
+        hipLaunchKernelGGL((k_xspec<H, C, true, XBank>), dim3(groups), dim3(G::NT), G::lds_bytes(), s, U, V, part, twH, N,
+                           colblocks, P, ppg, *xb);
+        if (colblocks > 1)
+            hipLaunchKernelGGL((k_xspec<H, C, false, XBank>), dim3(groups * (colblocks - 1)), dim3(G::NT), G::lds_bytes(), s,
+                               U, V, part, twH, N, colblocks, P, ppg, *xb);
+        return launch_check("k_xspec<bank>");
+    }
     const int groups = (P + ppg - 1) / ppg;
     if (int e = set_lds(k_xspec<H, C, true>, G::lds_bytes())) return e;
     if (int e = set_lds(k_xspec<H, C, false>, G::lds_bytes())) return e;
@@ -634,14 +656,16 @@ template <int H, int C> int xspec_hc(const cf* U, const cf* V, cf* part, const c
                            V, part, twH, N, colblocks, P, ppg);
     return launch_check("k_xspec");
 }
-template <int H> int xspec_h(const cf* U, const cf* V, cf* part, const cf* twH, int N, int P, int ppg, hipStream_t s) {
+template <int H> int xspec_h(const cf* U, const cf* V, cf* part, const cf* twH, int N, int P, int ppg, hipStream_t s,
+                             const XBank* xb, int T) {
     constexpr int L = ColGeom<H, 1>::L;
-    if constexpr (L <= 64) return xspec_hc<H, 8>(U, V, part, twH, N, P, ppg, s);
-    else if constexpr (L == 128) return xspec_hc<H, 8>(U, V, part, twH, N, P, ppg, s);
-    else return xspec_hc<H, 4>(U, V, part, twH, N, P, ppg, s);
+    if constexpr (L <= 64) return xspec_hc<H, 8>(U, V, part, twH, N, P, ppg, s, xb, T);
+    else if constexpr (L == 128) return xspec_hc<H, 8>(U, V, part, twH, N, P, ppg, s, xb, T);
+    else return xspec_hc<H, 4>(U, V, part, twH, N, P, ppg, s, xb, T);
 }
-int xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N, int P, int ppg, hipStream_t s) {
-    return with_col(H, [&](auto h) { return xspec_h<decltype(h)::value>(U, V, part, twH, N, P, ppg, s); });
+int xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N, int P, int ppg, hipStream_t s,
+          const XBank* xb = nullptr, int T = 0) {
+    return with_col(H, [&](auto h) { return xspec_h<decltype(h)::value>(U, V, part, twH, N, P, ppg, s, xb, T); });
 }
 
 // grouped modules train only on the fused power-of-two path (a smooth size solves them one after
@@ -671,10 +695,18 @@ int validate(const admm_tv_desc* d) {
 // what a PSF bank refuses (after validate, before any other check, in every entry point, size query and
 // admm_tv_path alike).  train: a training entry point; f64: an *_f64 entry point
 int bank_check(const admm_tv_desc& d, bool train = false, bool f64 = false) {
-    if (!is_bank(d)) return 0;
+    // training with a bank is opted into (ADMM_TV_FLAG_PSF_BANK_TRAIN): without the bit a bank answers as it did
+    // before the bit existed, so a caller can probe an older library of the same ABI version with bank | bit
+    const bool bt = (d.flags & ADMM_TV_FLAG_PSF_BANK_TRAIN) != 0;
+    if (!is_bank(d)) {
+        if (bt) return fail(ADMM_TV_EINVAL, "ADMM_TV_FLAG_PSF_BANK_TRAIN without a PSF bank (ADMM_TV_FLAG_PSF_PER_IMAGE / _PER_CHANNEL)");
+        return 0;
+    }
     if (f64 || is_f64(d)) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: fp32 only (ADMM_TV_FLAG_F64 / an _f64 entry point)");
-    if (train) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: inference only (training with a bank is not implemented)");
-    if (d.flags & ADMM_TV_FLAG_PSF_GRAD) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: no PSF gradient (ADMM_TV_FLAG_PSF_GRAD)");
+    if (train && !bt)
+        return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: inference only without ADMM_TV_FLAG_PSF_BANK_TRAIN (training with a bank is opt-in)");
+    if ((d.flags & ADMM_TV_FLAG_PSF_GRAD) && !bt)
+        return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: no PSF gradient (ADMM_TV_FLAG_PSF_GRAD) without ADMM_TV_FLAG_PSF_BANK_TRAIN");
     if (d.kh == 0) return fail(ADMM_TV_EINVAL, "PSF bank without a PSF (kh == 0)");
     if (d.groups > 1) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: groups > 1 (one solve per module)");
     if (d.allreduce) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: no cross-rank all-reduce hook");
@@ -690,15 +722,33 @@ double spectra_scale(int H, int W) {
     return (supported_hw(H, W) ? 0.5 : 1.0) / ((double)H * (double)W);
 }
 
+// k_spectra_bank with every table's sigma kept (training with a bank and a PSF gradient: T sigma tables, table after
+// table).  Defined here, in the one unit that launches it, so that the shared header's kernels compile as before.
+static __global__ void k_spectra_bank_sigma(const double2* __restrict__ G, const double2* __restrict__ twHd,
+                                            const float* __restrict__ rho_p, float* __restrict__ fcT,
+                                            cf* __restrict__ mT, int k, int H, int N, int W,
+                                            double2* __restrict__ sigma_out, double scale) {
+    const size_t n = (size_t)(N + 1) * H;
+    spectra_body<float>(G + (size_t)blockIdx.y * k * (N + 1), twHd, rho_p, fcT + blockIdx.y * n, mT + blockIdx.y * n, k, H,
+                        N, W, sigma_out + blockIdx.y * n, scale);
+}
+
 // The PSF tables of a bank (setup's PSF part, after its twiddle tables): every kernel takes its table from the
 // grid's second dimension, so a bank of B C PSFs is set up by the launches one PSF takes.  rho is the bank's.
 // bank_spectra: the Wiener factors into fcT (T tables) and the H_t multipliers (with their smooth-size copy).
 int bank_spectra(const admm_tv_desc& d, const Layout& Lo, void* ws, const float* rho, float* fcT, hipStream_t s) {
     const int H = (int)d.H, W = (int)d.W, N = W / 2, nt = 256, n = (N + 1) * H;
     const unsigned T = (unsigned)bank_of(d).T;
-    hipLaunchKernelGGL(k_spectra_bank, dim3((n + nt - 1) / nt, T), dim3(nt), 0, s, at<double2>(ws, Lo.G),
-                       at<double2>(ws, Lo.twHd), rho, fcT, at<cf>(ws, Lo.mT), d.kh, H, N, W, spectra_scale(H, W));
-    if (int e = launch_check("k_spectra_bank")) return e;
+    if (Lo.sigma) {  // training with a PSF gradient: every table's sigma is kept
+        hipLaunchKernelGGL(k_spectra_bank_sigma, dim3((n + nt - 1) / nt, T), dim3(nt), 0, s, at<double2>(ws, Lo.G),
+                           at<double2>(ws, Lo.twHd), rho, fcT, at<cf>(ws, Lo.mT), d.kh, H, N, W, at<double2>(ws, Lo.sigma),
+                           spectra_scale(H, W));
+        if (int e = launch_check("k_spectra_bank_sigma")) return e;
+    } else {
+        hipLaunchKernelGGL(k_spectra_bank, dim3((n + nt - 1) / nt, T), dim3(nt), 0, s, at<double2>(ws, Lo.G),
+                           at<double2>(ws, Lo.twHd), rho, fcT, at<cf>(ws, Lo.mT), d.kh, H, N, W, spectra_scale(H, W));
+        if (int e = launch_check("k_spectra_bank")) return e;
+    }
     if (Lo.mixed) return hip_code(admm_mixed::mt_mixed(at<cf>(ws, Lo.mT), at<cf>(ws, Lo.mM), H, N, s, (int)T), "k_mt_mixed_bank");
     return 0;
 }
@@ -1440,27 +1490,29 @@ int gcol_bank_launch(const GColBankArgs& a, size_t lds, dim3 grid, hipStream_t s
     return launch_check("k_gcol_bank");
 }
 
-// bank, p0: a PSF bank's table index and the solve's plane that the launch's plane 0 is (fp32, modes 0 and 1)
+// bank, p0: a PSF bank's table index and the solve's plane that the launch's plane 0 is (fp32; modes 0, 1 and the
+// training backward's 2, with or without a dump)
 template <class T>
 int gcol(cx_t<T>* spec, cx_t<T>* dump, const T* fcT, const cx_t<T>* mT, const cx_t<T>* tw, int H, int W, long long P,
          int mode, hipStream_t s, cx_t<T>* gscr, const MMPlan& mm, int ldw = 0, const BankIdx* bank = nullptr,
          long long p0 = 0) {
     if constexpr (!kF64<T>) {
-        if (bank) {
-            if (mm.ok || dump || mode > 1) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: the LDS column pass, inference only");
+        if (bank && mode != 3) {  // (mode 3 multiplies by nothing: the plain kernel below)
+            if (mm.ok) return fail(ADMM_TV_EUNSUPPORTED, "PSF bank: the LDS column pass only");
             const GPlan pl = make_plan(H, false);
             GLB_CHECK(pl, gscr)
             const int Wh = W / 2 + 1, cols = gcol_cols(H, pl);
             if (ldw && ldw != Wh) return fail(ADMM_TV_EINVAL, "padded spectrum pitch without the matrix-core column pass");
             const int colblocks = (Wh + cols - 1) / cols;
-            const GColBankArgs a{{spec, nullptr, fcT, mT, tw, pl, Wh, cols, colblocks, P, gscr}, *bank, p0};
+            const GColBankArgs a{{spec, dump, fcT, mT, tw, pl, Wh, cols, colblocks, P, gscr}, *bank, p0};
             const size_t lds = glds(H, cols, pl);
             const dim3 grid = gen_grid(P * colblocks, pl, sizeof(cf));
             return with_plan(pl, [&](auto bm, auto twg, auto glb) {
                 constexpr int BM = decltype(bm)::value;
                 constexpr bool TWG = decltype(twg)::value, GLB = decltype(glb)::value;
-                return mode == 0 ? gcol_bank_launch<0, BM, TWG, GLB>(a, lds, grid, s)
-                                 : gcol_bank_launch<1, BM, TWG, GLB>(a, lds, grid, s);
+                return mode == 0   ? gcol_bank_launch<0, BM, TWG, GLB>(a, lds, grid, s)
+                       : mode == 1 ? gcol_bank_launch<1, BM, TWG, GLB>(a, lds, grid, s)
+                                   : gcol_bank_launch<2, BM, TWG, GLB>(a, lds, grid, s);
             });
         }
     }
@@ -1973,8 +2025,10 @@ struct Pow2Ops : FusedOps {
     }
     // cross-spectrum partials for the PSF gradient (weighted: the A terms, which k_xspec_reduce weights by
     // fcT^2 -- fcT is stored / (2HW) here, so no factor is due)
-    int xspec(const cf* U, const cf* V, cf* part, long long P, int ppg, bool /*weighted*/, hipStream_t s) const {
-        return ::xspec(H, U, V, part, twH, N, (int)P, ppg, s);  // the free launcher above
+    // (xb: a PSF bank's gradient, the plane groups per table)
+    int xspec(const cf* U, const cf* V, cf* part, long long P, int ppg, bool /*weighted*/, hipStream_t s,
+              const XBank* xb = nullptr) const {
+        return ::xspec(H, U, V, part, twH, N, (int)P, ppg, s, xb, xb ? bank_of(d).T : 0);  // the free launcher above
     }
     int iso_norm(const IsoArgs& a, bool first, bool hist, hipStream_t s, bool pl) const {
         return with_row(N, [&](auto ops) { return decltype(ops)::iso_norm(a, first, hist, s, pl); });
@@ -2033,8 +2087,11 @@ struct MixedOps : FusedOps {
     // which is laid out [ky][kx] and so cannot be fed to the reduce): the missing (1/2)^2 goes on the
     // partials instead, the kernel's scale 0.25 (a power of two: exact), so that A = fc^2 Re(conj(X^) R) /
     // (HW)^2 and A_true = (HW)^2 A holds as k_psf_grad expects.
-    int xspec(const cf* U, const cf* V, cf* part, long long P, int ppg, bool weighted, hipStream_t s) const {
-        return hip_code(admm_mixed::xspec(H, U, V, part, twH, N, P, ppg, weighted ? 0.25f : 1.f, s), "k_xspec_m");
+    int xspec(const cf* U, const cf* V, cf* part, long long P, int ppg, bool weighted, hipStream_t s,
+              const XBank* xb = nullptr) const {
+        return hip_code(admm_mixed::xspec(H, U, V, part, twH, N, P, ppg, weighted ? 0.25f : 1.f, s, xb,
+                                          xb ? bank_of(d).T : 0),
+                        "k_xspec_m");
     }
     int iso_norm(const IsoArgs& a, bool first, bool hist, hipStream_t s, bool) const {
         return hip_code(admm_mixed::iso_norm(N, a, first, hist, s), "k_iso_norm_m");
@@ -2244,8 +2301,9 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
 
 // what a stateful solve refuses (admm_tv_forward_state, admm_tv_state_workspace_size, admm_tv_path(desc, 2))
 int state_check(const admm_tv_desc& d) {
-    if (d.flags & (ADMM_TV_FLAG_F64 | ADMM_TV_FLAG_PSF_GRAD))
-        return fail(ADMM_TV_EINVAL, "admm_tv_forward_state: fp32 inference only (ADMM_TV_FLAG_F64 / ADMM_TV_FLAG_PSF_GRAD set)");
+    if (d.flags & (ADMM_TV_FLAG_F64 | ADMM_TV_FLAG_PSF_GRAD | ADMM_TV_FLAG_PSF_BANK_TRAIN))
+        return fail(ADMM_TV_EINVAL, "admm_tv_forward_state: fp32 inference only (ADMM_TV_FLAG_F64 / ADMM_TV_FLAG_PSF_GRAD / "
+                                    "ADMM_TV_FLAG_PSF_BANK_TRAIN set)");
     if (d.groups > 1) return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_state: groups > 1 (one stateful solve per module)");
     if (d.allreduce) return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_state: no cross-rank all-reduce hook");
     // the state kernels run one block row per image row (as the generic step kernel does): B C H < 2^31.  Checked
@@ -2283,6 +2341,8 @@ int run_forward_state(const admm_tv_desc& d, const float* xin, const float* kern
 struct BwdLayout {
     Layout f;
     size_t abar[4], bbar, part, tpart, q, xpart, aacc, zacc, total;
+    // a PSF bank's gradient: the taps' phase tables Eh [k][H], Ew [k][W/2 + 1] and stage-1 sums [T][k][W/2 + 1]
+    size_t tapE, tapS;
     long long nstrips;
     int R, ntp, xgroups, xppg;
 };
@@ -2324,14 +2384,41 @@ BwdLayout make_bwd_layout(const admm_tv_desc& d) {
         B.xgroups = (int)((d.B * d.C + B.xppg - 1) / B.xppg);
         // fused paths: per-plane-group cross-spectrum partials; generic: one 2-D spectrum set
         const bool generic_x = B.f.gen && !B.f.mixed_train;
+        // a PSF bank: plane groups of one table each (T x cpt of them), A_t real fp64 and Z_t complex fp64 per table
+        // -- 24 bytes per half-spectrum point and table -- and the separable taps' phase tables and k rows of
+        // W/2 + 1 complex fp64 sums per table
+        const bool bank = is_bank(d);
+        const size_t T = bank ? (size_t)bank_of(d).T : 1, k = (size_t)d.kh, N1 = (size_t)d.W / 2 + 1;
+        if (bank) B.xgroups = (int)T * xbank_of(d, B.xppg).cpt;
         B.xpart = take((generic_x ? (size_t)d.B * d.C : (size_t)B.xgroups) * nf * 2 * rs);
-        B.aacc = take(nf * sizeof(double2));
-        B.zacc = take(nf * sizeof(double2));
+        B.aacc = take(bank ? T * nf * sizeof(double) : nf * sizeof(double2));
+        B.zacc = take(T * nf * sizeof(double2));
+        if (bank) {
+            B.tapE = take(k * ((size_t)d.H + N1) * sizeof(double2));
+            B.tapS = take(T * k * N1 * sizeof(double2));
+        }
     }
     B.total = o;
     return B;
 }
 
+
+// A PSF bank's taps from its per-table accumulators (A_t at BL.aacc, Z_t at BL.zacc, sigma_t at Layout::sigma):
+// the phase tables once, then the two separable stages (admm_backward.hpp).  gkern: T kh kw floats, bank order.
+int bank_taps(const admm_tv_desc& d, const BwdLayout& BL, void* ws, float* gkern, double zscale, hipStream_t s) {
+    const int H = (int)d.H, W = (int)d.W, N1 = W / 2 + 1, k = d.kh;
+    const unsigned T = (unsigned)bank_of(d).T;
+    double2* Eh = at<double2>(ws, BL.tapE);
+    double2* Ew = Eh + (size_t)k * H;
+    const long long ne = (long long)k * (H + N1);
+    hipLaunchKernelGGL(k_tap_tables, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, Eh, Ew, k, H, W);
+    if (int e = launch_check("k_tap_tables")) return e;
+    hipLaunchKernelGGL(k_psf_taps_col, dim3((unsigned)N1, T), dim3(256), 0, s, at<double>(ws, BL.aacc),
+                       at<double2>(ws, BL.zacc), at<double2>(ws, BL.f.sigma), Eh, Ew, at<double2>(ws, BL.tapS), k, H, W, zscale);
+    if (int e = launch_check("k_psf_taps_col")) return e;
+    hipLaunchKernelGGL(k_psf_taps_row, dim3((unsigned)(k * k), T), dim3(256), 0, s, at<double2>(ws, BL.tapS), Ew, k, W, gkern);
+    return launch_check("k_psf_taps_row");
+}
 
 // generic-size backward (same contract as admm_tv_backward, PSF gradient excluded)
 template <class T>
@@ -2348,7 +2435,12 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
     const int Wh = W / 2 + 1;
     const long long nf = (long long)Wh * H;
     C* xspec = psf_grad ? at<C>(ws, BL.xpart) : nullptr;  // 2-D spectra of x^_k (then of b^)
-    if (psf_grad) {
+    const bool bank = is_bank(d);  // fp32 (bank_check): each plane's table, the PSF gradient per table
+    const BankIdx bk = bank_of(d);
+    const BankIdx* const bankp = bank ? &bk : nullptr;
+    if (psf_grad && bank) {
+        HIPCHK(hipMemsetAsync(at<double>(ws, BL.aacc), 0, (size_t)bk.T * nf * sizeof(double), s));
+    } else if (psf_grad) {
         HIPCHK(hipMemsetAsync(at<double2>(ws, BL.aacc), 0, nf * sizeof(double2), s));
         HIPCHK(hipMemsetAsync(at<double2>(ws, BL.zacc), 0, nf * sizeof(double2), s));
     }
@@ -2377,9 +2469,16 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
             // r^_k = M x^_k; with the PSF gradient the column pass also dumps X^_k's spectrum and
             // A += fc^2 Re(sum_p conj(X^_k) R_k)
             if (int e = grow_fwd(xbk, spec, twW, W, rows, s, gs)) return e;
-            if (int e = gcol<T>(spec, xspec, fcT, at<C>(ws, Lo.mT), twH, H, W, P, 0, s, gs, Lo.mm)) return e;
+            if (int e = gcol<T>(spec, xspec, fcT, at<C>(ws, Lo.mT), twH, H, W, P, 0, s, gs, Lo.mm, 0, bankp)) return e;
             if (int e = grow_inv<T>(spec, rb, twW, W, rows, s, gs, Lo.mmr)) return e;
-            if (psf_grad) {
+            if constexpr (!kF64<T>) {
+                if (psf_grad && bank) {  // A_t += fc_t^2 Re(sum over table t's planes of conj(X^_k) R_k)
+                    hipLaunchKernelGGL(k_gxspec_acc_bank, dim3(fgrid.x, (unsigned)bk.T), fblk, 0, s, xspec, hv.r(k),
+                                       xbank_of(d, BL.xppg), H, Wh, fcT, at<double>(ws, BL.aacc), (double2*)nullptr);
+                    if (int e = launch_check("k_gxspec_acc_bank")) return e;
+                }
+            }
+            if (psf_grad && !bank) {
                 hipLaunchKernelGGL(k_gxspec_acc<T>, fgrid, fblk, 0, s, xspec, hv.r(k), P, H, Wh, fcT, at<double2>(ws, BL.aacc));
                 if (int e = launch_check("k_gxspec_acc")) return e;
             }
@@ -2425,11 +2524,22 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
         if (int e = gcol<T>(spec, xspec, nullptr, nullptr, twH, H, W, P, 3, s, gs, Lo.mm)) return e;
         if (int e = grow_fwd(xin, spec, twW, W, rows, s, gs)) return e;
         if (int e = gcol<T>(spec, spec, nullptr, nullptr, twH, H, W, P, 3, s, gs, Lo.mm)) return e;
-        hipLaunchKernelGGL(k_gxspec_acc<T>, fgrid, fblk, 0, s, xspec, spec, P, H, Wh, nullptr, at<double2>(ws, BL.zacc));
-        if (int e = launch_check("k_gxspec_acc")) return e;
-        hipLaunchKernelGGL(k_psf_grad<T>, dim3(d.kh * d.kw), dim3(256), 0, s, at<double2>(ws, BL.aacc),
-                           at<double2>(ws, BL.zacc), at<double2>(ws, Lo.sigma), d.kh, H, W, gkern, 1.0);
-        if (int e = launch_check("k_psf_grad")) return e;
+        if constexpr (!kF64<T>) {
+            if (bank) {
+                hipLaunchKernelGGL(k_gxspec_acc_bank, dim3(fgrid.x, (unsigned)bk.T), fblk, 0, s, xspec, spec,
+                                   xbank_of(d, BL.xppg), H, Wh, (const float*)nullptr, (double*)nullptr,
+                                   at<double2>(ws, BL.zacc));
+                if (int e = launch_check("k_gxspec_acc_bank")) return e;
+                if (int e = bank_taps(d, BL, ws, gkern, 1.0, s)) return e;
+            }
+        }
+        if (!bank) {
+            hipLaunchKernelGGL(k_gxspec_acc<T>, fgrid, fblk, 0, s, xspec, spec, P, H, Wh, nullptr, at<double2>(ws, BL.zacc));
+            if (int e = launch_check("k_gxspec_acc")) return e;
+            hipLaunchKernelGGL(k_psf_grad<T>, dim3(d.kh * d.kw), dim3(256), 0, s, at<double2>(ws, BL.aacc),
+                               at<double2>(ws, BL.zacc), at<double2>(ws, Lo.sigma), d.kh, H, W, gkern, 1.0);
+            if (int e = launch_check("k_psf_grad")) return e;
+        }
     }
     if (gxin && d.kh > 0)  // x^_in = H_t^T b^
         if (int e = gapply<T>(bbar, gxin, spec, Lo, ws, d, 2, s)) return e;
@@ -2453,7 +2563,15 @@ int fused_backward(const B& be, const BwdLayout& BL, const float* xin, const flo
     const HistView<float> hv(d, hist);
     const bool psf_grad = B::kPsfGrad && gkern != nullptr;
     const long long nf = (long long)(N + 1) * H;
-    if (psf_grad) {
+    // a PSF bank (one module): the cross spectra in plane groups of one table each, reduced per table
+    // (BL.xppg is set with the PSF gradient only: no chunks to count without it)
+    const bool bank = is_bank(d);
+    const XBank xb = (bank && psf_grad) ? xbank_of(d, BL.xppg) : XBank{1, 1, 1, 1};
+    const XBank* const xbp = bank ? &xb : nullptr;
+    const unsigned nT = bank ? (unsigned)bank_of(d).T : 1;
+    if (psf_grad && bank) {
+        HIPCHK(hipMemsetAsync(at<double>(ws, BL.aacc), 0, (size_t)nT * nf * sizeof(double), s));
+    } else if (psf_grad) {
         HIPCHK(hipMemsetAsync(at<double2>(ws, BL.aacc), 0, nf * sizeof(double2), s));
         HIPCHK(hipMemsetAsync(at<double2>(ws, BL.zacc), 0, nf * sizeof(double2), s));
     }
@@ -2470,7 +2588,13 @@ int fused_backward(const B& be, const BwdLayout& BL, const float* xin, const flo
     if (int e = be.r2c(gout, spec[0], rows, s)) return e;
     int cur = 0, ain = 0;
     for (int k = K; k >= 1; --k) {
-        if (psf_grad) {  // A += fc^2 Re(sum_p conj(X^_k) R_k), before the column pass rewrites X^_k
+        if (psf_grad && bank) {  // A_t += fc_t^2 Re(sum over table t's planes), as below
+            if (int e = be.xspec(spec[cur], hv.r(k), at<cf>(ws, BL.xpart), P, BL.xppg, true, s, xbp)) return e;
+            hipLaunchKernelGGL(k_xspec_reduce_bank, dim3((unsigned)((nf + 255) / 256), nT), dim3(256), 0, s,
+                               at<cf>(ws, BL.xpart), xb.cpt, nf, at<float>(ws, Lo.fcT), at<double>(ws, BL.aacc),
+                               (double2*)nullptr);
+            if (int e = launch_check("k_xspec_reduce_bank")) return e;
+        } else if (psf_grad) {  // A += fc^2 Re(sum_p conj(X^_k) R_k), before the column pass rewrites X^_k
             if (int e = be.xspec(spec[cur], hv.r(k), at<cf>(ws, BL.xpart), P, BL.xppg, true, s)) return e;
             hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s,
                                at<cf>(ws, BL.xpart), BL.xgroups, nf, at<float>(ws, Lo.fcT), at<double2>(ws, BL.aacc));
@@ -2526,13 +2650,22 @@ int fused_backward(const B& be, const BwdLayout& BL, const float* xin, const flo
     if (psf_grad) {  // Z = sum_p conj(Bbar_p) Xin_p, then the k x k taps
         if (int e = be.r2c(bbar, spec[0], rows, s)) return e;
         if (int e = be.r2c(xin, spec[1], rows, s)) return e;
-        if (int e = be.xspec(spec[0], spec[1], at<cf>(ws, BL.xpart), P, BL.xppg, false, s)) return e;
-        hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, at<cf>(ws, BL.xpart),
-                           BL.xgroups, nf, nullptr, at<double2>(ws, BL.zacc));
-        if (int e = launch_check("k_xspec_reduce")) return e;
-        hipLaunchKernelGGL(k_psf_grad<float>, dim3(d.kh * d.kw), dim3(256), 0, s, at<double2>(ws, BL.aacc),
-                           at<double2>(ws, BL.zacc), at<double2>(ws, Lo.sigma), d.kh, H, W, gkern, 0.25);
-        if (int e = launch_check("k_psf_grad")) return e;
+        if (bank) {  // Z_t per table, then the separable taps
+            if (int e = be.xspec(spec[0], spec[1], at<cf>(ws, BL.xpart), P, BL.xppg, false, s, xbp)) return e;
+            hipLaunchKernelGGL(k_xspec_reduce_bank, dim3((unsigned)((nf + 255) / 256), nT), dim3(256), 0, s,
+                               at<cf>(ws, BL.xpart), xb.cpt, nf, (const float*)nullptr, (double*)nullptr,
+                               at<double2>(ws, BL.zacc));
+            if (int e = launch_check("k_xspec_reduce_bank")) return e;
+            if (int e = bank_taps(d, BL, ws, gkern, 0.25, s)) return e;
+        } else {
+            if (int e = be.xspec(spec[0], spec[1], at<cf>(ws, BL.xpart), P, BL.xppg, false, s)) return e;
+            hipLaunchKernelGGL(k_xspec_reduce, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, at<cf>(ws, BL.xpart),
+                               BL.xgroups, nf, nullptr, at<double2>(ws, BL.zacc));
+            if (int e = launch_check("k_xspec_reduce")) return e;
+            hipLaunchKernelGGL(k_psf_grad<float>, dim3(d.kh * d.kw), dim3(256), 0, s, at<double2>(ws, BL.aacc),
+                               at<double2>(ws, BL.zacc), at<double2>(ws, Lo.sigma), d.kh, H, W, gkern, 0.25);
+            if (int e = launch_check("k_psf_grad")) return e;
+        }
     }
     if (gxin && G > 1) {  // the modules share xin: x^_in collects every module's b^
         const long long n4 = Pm * H * W / 4;
@@ -2564,7 +2697,7 @@ int run_backward(const admm_tv_desc& d, const float* xin, const float* kern, con
         if (gxin) HIPCHK(hipMemsetAsync(gxin, 0, img_bytes, s));
         if (glam) HIPCHK(hipMemsetAsync(glam, 0, sizeof(float) * G, s));
         if (grho) HIPCHK(hipMemsetAsync(grho, 0, sizeof(float) * G, s));
-        if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(float) * d.kh * d.kw, s));
+        if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(float) * (is_bank(d) ? bank_of(d).T : 1) * d.kh * d.kw, s));
         return 0;
     }
     if (participate_only(d)) {  // the same reductions as the iso backward, contributing zeros

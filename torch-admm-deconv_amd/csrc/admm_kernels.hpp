@@ -154,6 +154,15 @@ __device__ __forceinline__ int bank_tab(long long p, const BankIdx& bk) { return
 __device__ __forceinline__ int bank_tables(int one) { return one; }
 __device__ __forceinline__ int bank_tables(int, const BankIdx& bk) { return bk.T; }
 
+// The planes of one table, for the bank's PSF gradient (the cross-spectrum kernels' trailing argument): table t
+// owns the n planes t tb + j stride, j < n -- a per-image bank C consecutive planes (tb = C, stride 1), a
+// per-channel bank B planes at stride C (tb = 1), a per-plane bank one plane.  They are summed in chunks of the
+// kernels' ppg planes, cpt = ceil(n / ppg) chunks per table: plane group g is chunk g % cpt of table g / cpt,
+// so a group never holds planes of two tables and a table's partials lie next to one another.
+struct XBank {
+    int tb, stride, n, cpt;
+};
+
 // G[a][kx] = sum_b kern[a][b] exp(-2 pi i b kx / W), kx in [0, N], in fp64
 template <class T>
 __device__ __forceinline__ void psf_rows_body(const T* __restrict__ kern, double2* __restrict__ G, int k, int N, int W) {

@@ -678,7 +678,7 @@ __global__ void __launch_bounds__(NT, gcol_minw(BM)) k_gcol(GColArgsT<T> a) {
     ADMM_GEN_ITEMS(a.P * a.colblocks, 1, ADMM_ITEM)
 #undef ADMM_ITEM
 }
-// ... of a PSF bank (fp32 inference and H_t: MODE 0 and 1)
+// ... of a PSF bank (fp32: MODE 0 and 1, and the training backward's MODE 2)
 template <int MODE, int BM, bool TWG, int NT = GNT, bool GLB = false>
 __global__ void __launch_bounds__(NT, gcol_minw(BM)) k_gcol_bank(GColBankArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1034,6 +1034,30 @@ __global__ void k_gxspec_acc(const cx_t<T>* __restrict__ U, const cx_t<T>* __res
     } else {
         acc[i].x += re;
         acc[i].y += im;
+    }
+}
+// ... of a PSF bank: table blockIdx.y sums its own planes (XBank: n planes t tb + j stride, in order) into its
+// accumulator -- A_t (real, += with table t's fcT) or Z_t (complex, written once); see admm_backward.hpp
+static __global__ void k_gxspec_acc_bank(const cf* __restrict__ U, const cf* __restrict__ V, XBank xb, int H, int Wh,
+                                         const float* __restrict__ fcT, double* __restrict__ accA,
+                                         double2* __restrict__ accZ) {
+    const long long nf = (long long)H * Wh;
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nf) return;
+    const int ky = (int)(f / Wh), kx = (int)(f % Wh);
+    double re = 0.0, im = 0.0;
+    for (int j = 0; j < xb.n; ++j) {
+        const long long p = (long long)blockIdx.y * xb.tb + (long long)j * xb.stride;
+        const cf u = U[p * nf + f], v = V[p * nf + f];
+        re += (double)u.x * v.x + (double)u.y * v.y;
+        im += (double)u.x * v.y - (double)u.y * v.x;
+    }
+    const size_t i = (size_t)blockIdx.y * nf + (size_t)kx * H + ky;
+    if (fcT) {
+        const double c = fcT[i];
+        accA[i] += c * c * re;
+    } else {
+        accZ[i] = make_double2(re, im);
     }
 }
 

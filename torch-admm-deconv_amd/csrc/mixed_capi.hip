@@ -251,8 +251,14 @@ hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH,
                               : CC >= 8   ? (int)std::min<long long>(P, 1 << 30)
                                           : 2;
             const int colblocks = N / CC;
-            if (bank) {  // one launch over all planes, each with its table (inference: in place)
-                if (in != out) return hipErrorInvalidValue;
+            if (bank && in != out) {  // ... out of place (training with a bank and a PSF gradient: r_k stays)
+                if (hipError_t e = lds(k_pass_b_m<HH, CC, false, true, admm::BankIdx>, G::lds_bytes())) return e;
+                hipLaunchKernelGGL((k_pass_b_m<HH, CC, false, true, admm::BankIdx>), dim3((unsigned)(P * colblocks)),
+                                   dim3(G::NT), G::lds_bytes(), s, const_cast<cf*>(in), fcM, twH, N, colblocks, order, fpack,
+                                   nullptr, out, *bank);
+                return hipGetLastError();
+            }
+            if (bank) {  // one launch over all planes, each with its table (in place)
                 if (hipError_t e = lds(k_pass_b_m<HH, CC, false, false, admm::BankIdx>, G::lds_bytes())) return e;
                 hipLaunchKernelGGL((k_pass_b_m<HH, CC, false, false, admm::BankIdx>), dim3((unsigned)(P * colblocks)),
                                    dim3(G::NT), G::lds_bytes(), s, out, fcM, twH, N, colblocks, order, fpack, nullptr,
@@ -326,13 +332,24 @@ template <int H> struct XspecC {
     static constexpr int value = C0 * Lc <= 512 ? C0 : (C0 > 4 && 4 * Lc <= 512) ? 4 : 2;
 };
 hipError_t xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N, long long P, int ppg, float scale,
-                 hipStream_t s) {
+                 hipStream_t s, const admm::XBank* xb, int tables) {
     return with_col(H, [&](auto h) {
         constexpr int HH = decltype(h)::value;
         auto go = [&](auto cc) {
             constexpr int CC = decltype(cc)::value;
             using G = MColG<HH, CC>;
             const int colblocks = N / CC;
+            if (xb) {  // a bank: tables x cpt plane groups, each inside one table
+                const unsigned groups = (unsigned)tables * (unsigned)xb->cpt;
+                if (hipError_t e = lds(k_xspec_m<HH, CC, true, admm::XBank>, G::lds_bytes())) return e;
+                if (hipError_t e = lds(k_xspec_m<HH, CC, false, admm::XBank>, G::lds_bytes())) return e;
+                hipLaunchKernelGGL((k_xspec_m<HH, CC, true, admm::XBank>), dim3(groups), dim3(G::NT), G::lds_bytes(), s, U, V,
+                                   part, twH, N, colblocks, (int)P, ppg, scale, *xb);
+                if (colblocks > 1)
+                    hipLaunchKernelGGL((k_xspec_m<HH, CC, false, admm::XBank>), dim3(groups * (unsigned)(colblocks - 1)),
+                                       dim3(G::NT), G::lds_bytes(), s, U, V, part, twH, N, colblocks, (int)P, ppg, scale, *xb);
+                return hipGetLastError();
+            }
             const unsigned groups = (unsigned)((P + ppg - 1) / ppg);
             if (hipError_t e = lds(k_xspec_m<HH, CC, true>, G::lds_bytes())) return e;
             if (hipError_t e = lds(k_xspec_m<HH, CC, false>, G::lds_bytes())) return e;

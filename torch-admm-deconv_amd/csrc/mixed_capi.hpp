@@ -30,13 +30,14 @@ hipError_t bwd_pass_a(int N, const admm::BwdArgs& a, bool iso, bool lastk, bool 
 hipError_t bwd_iso_q(int N, const admm::BwdIsoArgs& a, bool lastk, hipStream_t s);
 // the column pass of P planes from `in` into `out`: the same buffer (in place), or -- the training forward with
 // a PSF gradient, whose r_k stay in the history -- another one
-// bank: a PSF bank's table index (fcM then holds bank->T tables; in place only), null for one PSF
+// bank: a PSF bank's table index (fcM then holds bank->T tables), null for one PSF
 hipError_t pass_b(int H, const cf* in, cf* out, const float* fcM, const cf* twH, int N, long long P, hipStream_t s,
                   const admm::BankIdx* bank = nullptr);
 // PSF gradient: part[g][kx][ky] = scale * sum over plane group g (ppg planes) of conj(colFFT U_p) colFFT V_p,
 // kx in [0, N] (k_xspec's layout: k_xspec_reduce and k_psf_grad follow)
+// xb: a PSF bank's gradient -- `tables` x xb->cpt plane groups, each a chunk of one table's planes (admm::XBank)
 hipError_t xspec(int H, const cf* U, const cf* V, cf* part, const cf* twH, int N, long long P, int ppg, float scale,
-                 hipStream_t s);
+                 hipStream_t s, const admm::XBank* xb = nullptr, int tables = 0);
 // fcM: [H][N + 1] then the column-block-packed copy [N / C][H][C] (C = pass_b_cols): H (2N + 1) floats
 // (tables > 0: a PSF bank's tables, one after another in fcT and in fcM, in one launch)
 hipError_t fc_mixed(const float* fcT, float* fcM, int H, int N, hipStream_t s, int tables = 0);

@@ -724,10 +724,11 @@ static __global__ void k_mt_mixed_bank(const cf* __restrict__ mT, cf* __restrict
 // After the forward schedule the frequencies sit in layout(Rz) (as in k_pass_b_m): register q + Qz k holds
 // ky = t + Lc q + NBz k, valid for t + Lc q < NBz only -- the padding lanes never store.
 // ---------------------------------------------------------------------------------------------
-template <int H, int CC, bool COL0>
+// (XB = XBank, one trailing argument: a PSF bank's gradient, plane groups of one table each, as k_xspec's)
+template <int H, int CC, bool COL0, class... XB>
 __global__ void __launch_bounds__((MColG<H, CC>::NT))
 k_xspec_m(const cf* __restrict__ U, const cf* __restrict__ V, cf* __restrict__ part, const cf* __restrict__ twH_g,
-          int N, int colblocks, int P, int ppg, float scale) {
+          int N, int colblocks, int P, int ppg, float scale, XB... xb) {
     using G = MColG<H, CC>;
     constexpr int Lc = G::Lc, Ec = G::Ec, C = G::C, EM = G::EM, NBz = G::NBz, Qz = G::Qz, Rz = G::Rz, NV = Qz * Rz;
     static_assert(C >= 2, "the column-0 split parks its two operands in two column slots");
@@ -750,10 +751,10 @@ k_xspec_m(const cf* __restrict__ U, const cf* __restrict__ V, cf* __restrict__ p
         for (int i = 0; i < NV; ++i) accn[i] = mkc(0.f, 0.f);
     }
     __syncthreads();  // twiddles in LDS
-    const int p1 = min(P, (grp + 1) * ppg);
-    for (int p = grp * ppg; p < p1; ++p) {
-        const cf* up = U + ((size_t)p * H + t) * N + col;
-        const cf* vp = V + ((size_t)p * H + t) * N + col;
+    const int p1 = xplanes_end(grp, ppg, P, xb...);
+    for (int p = xplanes_begin(grp, ppg, xb...); p < p1; ++p) {
+        const cf* up = U + (xplane(grp, p, xb...) * H + t) * N + col;
+        const cf* vp = V + (xplane(grp, p, xb...) * H + t) * N + col;
         cf u[EM], v[EM];
 #pragma unroll
         for (int j = 0; j < Ec; ++j) u[j] = up[(size_t)j * Lc * N];
