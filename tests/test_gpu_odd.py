@@ -120,7 +120,9 @@ def test_odd_graph_capture(cuda_dev):
 
 def test_odd_size_iso_and_training_keep_generic(cuda_dev):
     """iso and training at an odd size run on the generic kernels (admm_tv_path): still against the fp64
-    oracle, including the gradients of a short training solve."""
+    oracle, including the x and lambda gradients of a short training solve.  The full set at 481-point rows
+    (rho and the PSF too, aniso and iso, at fixed gates on inputs checked for them) is carried by the r481 cases
+    of tests/generic_train_cases.py, run by tests/test_gpu_generic_train.py."""
     from admmtor.eops.deconv import fft_admm_tv
     from admmtor.synth import blurred_batch, make_psf
     from oracle.admm_oracle import solve_fourier

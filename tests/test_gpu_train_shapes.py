@@ -35,18 +35,19 @@ def assert_fused(case):
     return d
 
 
-def hip_train(case, dev):
+def hip_train(case, dev, dtype=torch.float32):
     """fft_admm_tv with x, lambda, rho (and the PSF where learnable) requiring gradients, and its
-    gradients against the case's cotangent: dict(out, gx, glam, grho[, gk]) on the CPU."""
+    gradients against the case's cotangent: dict(out, gx, glam, grho[, gk]) on the CPU.  dtype: of every
+    input (torch.float64: the fp64 solve)."""
     from admmtor.eops.deconv import fft_admm_tv
     x, k = tc.inputs(case)
-    xg = x.to(dev).requires_grad_(True)
-    lam = torch.tensor([case.lam], device=dev, requires_grad=True)
-    rho = torch.tensor([case.rho], device=dev, requires_grad=True)
-    kg = k.to(dev).requires_grad_(case.learn_psf) if k.numel() else torch.empty(0, device=dev)
+    xg = x.to(dev, dtype).requires_grad_(True)
+    lam = torch.tensor([case.lam], device=dev, dtype=dtype, requires_grad=True)
+    rho = torch.tensor([case.rho], device=dev, dtype=dtype, requires_grad=True)
+    kg = k.to(dev, dtype).requires_grad_(case.learn_psf) if k.numel() else torch.empty(0, device=dev, dtype=dtype)
     out = fft_admm_tv(xg, lam, rho, kg, case.iso, case.maxit)
     wrt = (xg, lam, rho) + ((kg,) if case.learn_psf else ())
-    g = torch.autograd.grad(out, wrt, tc.cotangent(case).to(dev))
+    g = torch.autograd.grad(out, wrt, tc.cotangent(case).to(dev, dtype))
     torch.cuda.synchronize()
     got = dict(out=out.detach().cpu(), gx=g[0].cpu(), glam=g[1].cpu(), grho=g[2].cpu())
     if case.learn_psf:
