@@ -205,6 +205,25 @@ struct Layout {
     int ldw;
 };
 
+// The kernels a call runs on, decided here and nowhere else: admm_tv_path reports it, run_forward, run_backward
+// and run_forward_state switch on it, make_hist and make_bwd_layout size their regions by it.
+//   Pow2      the fused two-pass iteration, power-of-two sizes (Pow2Ops)
+//   Mixed     the same on the mixed-radix register transforms, smooth sizes (MixedOps)
+//   Generic   the generic kernels' three-launch iteration (run_forward_gen / run_backward_gen)
+//   OddRows   the generic column pass and the fused odd-length row pass (aniso inference)
+//   OddRowsT  OddRows on the transposed problem
+// mode: 0 inference, 1 training (forward with a history, backward), 2 stateful inference (fp32: state_check)
+enum class Backend { Pow2, Mixed, Generic, OddRows, OddRowsT };
+Backend backend_of(const admm_tv_desc& d, const Layout& Lo, int mode) {
+    if (mode != 2 && is_f64(d)) return Backend::Generic;  // the generic kernels' double instantiation
+    if (mode != 2 && Lo.tr) return mode == 0 ? Backend::OddRowsT : Backend::Generic;
+    if (!Lo.gen) return Backend::Pow2;
+    if (Lo.mixed && (mode != 1 || Lo.mixed_train)) return Backend::Mixed;
+    // (the odd-length row pass keeps no history and carries no state)
+    if (mode == 0 && Lo.odd) return Backend::OddRows;
+    return Backend::Generic;
+}
+
 // (transposes a single PSF's shape: never reached with a PSF bank, make_layout leaves Layout::tr unset for one)
 admm_tv_desc transposed(const admm_tv_desc& d) {
     admm_tv_desc t = d;
@@ -216,7 +235,7 @@ admm_tv_desc transposed(const admm_tv_desc& d) {
 }
 
 // a training step of this descriptor runs on the mixed-radix fused kernels: fp32, one module, a smooth size
-// (make_layout, make_hist and make_bwd_layout size their regions by it)
+// (Layout::mixed_train)
 bool mixed_train_hw(const admm_tv_desc& d) {
     return !is_f64(d) && ngroups_of(d) == 1 && generic_hw(d.H, d.W) && mixed_hw(d.H, d.W);
 }
@@ -1615,7 +1634,7 @@ struct Hist {
     bool keep_t;
     size_t total;
 };
-Hist make_hist(const admm_tv_desc& d) {
+Hist make_hist(const admm_tv_desc& d, const Layout& Lo) {
     Hist h{};
     const size_t rs = is_f64(d) ? sizeof(double) : sizeof(float);
     const size_t G = ngroups_of(d);
@@ -1625,8 +1644,7 @@ Hist make_hist(const admm_tv_desc& d) {
     h.n_off = (size_t)d.maxit * 2 * h.a_slot;
     h.t_off = h.n_off + (size_t)d.maxit * h.n_slot;
     h.keep_t = d.kh > 0 && (d.flags & ADMM_TV_FLAG_PSF_GRAD);
-    // (generic_hw is true at smooth sizes too: there the mixed-radix path keeps packed row spectra)
-    const bool generic_t = is_f64(d) || (generic_hw(d.H, d.W) && !mixed_train_hw(d));
+    const bool generic_t = backend_of(d, Lo, 1) == Backend::Generic;
     h.t_slot = generic_t ? up((size_t)d.B * d.C * d.H * (d.W / 2 + 1) * 2 * rs) : h.a_slot;
     h.total = h.t_off + (h.keep_t ? (size_t)d.maxit * h.t_slot : 0);
     return h;
@@ -1635,7 +1653,7 @@ Hist make_hist(const admm_tv_desc& d) {
 template <class T> struct HistView {
     Hist h;
     char* base;
-    HistView(const admm_tv_desc& d, const void* hist) : h(make_hist(d)), base(static_cast<char*>(const_cast<void*>(hist))) {}
+    HistView(const admm_tv_desc& d, const Layout& Lo, const void* hist) : h(make_hist(d, Lo)), base(static_cast<char*>(const_cast<void*>(hist))) {}
     T* a(int k, int comp) const {  // a_k image, comp 0 = x, 1 = y
         return reinterpret_cast<T*>(base + (size_t)(2 * (k - 1) + comp) * h.a_slot);
     }
@@ -1737,9 +1755,10 @@ int state_export(const admm_tv_desc& d, const Layout& Lo, void* ws, const float*
 
 
 // generic-size forward (same contract as run_forward; generic_kernels.hpp)
+// odd_rows (Backend::OddRows: fp32 aniso inference, no state): the two-launch iteration on the odd-length row pass
 template <class T>
-int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const T* lam, const T* rho, T* out, void* ws,
-                    void* hist, hipStream_t s, const StateIO* sio = nullptr) {
+int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, bool odd_rows, const T* xin, const T* lam, const T* rho,
+                    T* out, void* ws, void* hist, hipStream_t s, const StateIO* sio = nullptr) {
     using C = cx_t<T>;
     const long long P = d.B * d.C;
     const int H = (int)d.H, W = (int)d.W;
@@ -1753,7 +1772,7 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
     T* rimg = at<T>(ws, Lo.rimg);
     T* u[4] = {at<T>(ws, Lo.u[0]), at<T>(ws, Lo.u[1]), at<T>(ws, Lo.u[2]), at<T>(ws, Lo.u[3])};
     const bool train = hist != nullptr;
-    const HistView<T> hv(d, hist);
+    const HistView<T> hv(d, Lo, hist);
     const bool keep_t = train && hv.h.keep_t;  // PSF gradient: keep every r_k's 2-D spectrum
     const T* bimg = xin;
     if (d.kh > 0) {  // b = H_t(xin) once
@@ -1763,9 +1782,8 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         bimg = bb;
     }
     // a stateful solve (fp32 inference; fused_forward): r_1 from v = b + rho D^T (z0 - u0) in `out`, u0 the
-    // first iteration's u input; the odd-length row pass does not know about state, so such a solve keeps
-    // the three-launch iteration
-    const bool stateful = sio != nullptr, sin = sio && sio->in, sout = sio && sio->out;
+    // first iteration's u input
+    const bool sin = sio && sio->in, sout = sio && sio->out;
     const BankIdx bank = bank_of(d);
     const BankIdx* const bankp = is_bank(d) ? &bank : nullptr;
     const T* r1img = bimg;
@@ -1792,7 +1810,7 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, const T* xin, const
         if (int e = grow_fwd(r1img + io, cspec, twW, W, crows, st, gs, ld)) return e;  // r_1 = b (or from the state)
     }
     if constexpr (!kF64<T>) {
-        if (Lo.odd && !train && !stateful) {
+        if (odd_rows) {
             // the two-launch iteration (odd_kernels.hpp): the column pass in place on spec[cur], then pass A
             // (inverse rows, step, forward rows) from spec[cur] into spec[1 - cur]; u ping-pong as below
             C* sp[2] = {cspec, at<C>(ws, Lo.spec2) + so};
@@ -2151,7 +2169,7 @@ int fused_forward(const B& be, const float* xin, const float* lam, const float* 
     cf* spec[2] = {at<cf>(ws, Lo.spec[0]), at<cf>(ws, Lo.spec[1])};
     float* u[4] = {at<float>(ws, Lo.u[0]), at<float>(ws, Lo.u[1]), at<float>(ws, Lo.u[2]), at<float>(ws, Lo.u[3])};
     const bool train = hist != nullptr;
-    const HistView<float> hv(d, hist);
+    const HistView<float> hv(d, Lo, hist);
     const bool keep_t = B::kPsfGrad && train && hv.h.keep_t;
     const bool pl = be.lane_paired(train);
     const float* bimg = xin;
@@ -2255,7 +2273,8 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
                 float* out, void* ws, size_t ws_bytes, void* hist, hipStream_t s) {
     const Layout Lo = make_layout(d);
     if (int e = check_workspace(ws, ws_bytes, Lo.total)) return e;
-    if (Lo.tr && !hist && d.maxit > 0) {  // the transposed odd-length solve (odd_t_hw)
+    const Backend be = backend_of(d, Lo, hist ? 1 : 0);
+    if (be == Backend::OddRowsT && d.maxit > 0) {  // the transposed odd-length solve (odd_t_hw)
         const long long P = d.B * d.C;
         const int H = (int)d.H, W = (int)d.W;
         float* xT = at<float>(ws, Lo.xT);
@@ -2294,9 +2313,14 @@ int run_forward(const admm_tv_desc& d, const float* xin, const float* kern, cons
         return 0;
     }
     if (int e = setup(d, Lo, ws, kern, rho, s)) return e;
-    if (Lo.mixed && (!hist || Lo.mixed_train)) return fused_forward(MixedOps(d, Lo, ws), xin, lam, rho, out, hist, s);
-    if (Lo.gen) return run_forward_gen(d, Lo, xin, lam, rho, out, ws, hist, s);
-    return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, hist, s);
+    switch (be) {
+        case Backend::Pow2: return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, hist, s);
+        case Backend::Mixed: return fused_forward(MixedOps(d, Lo, ws), xin, lam, rho, out, hist, s);
+        case Backend::Generic: return run_forward_gen(d, Lo, false, xin, lam, rho, out, ws, hist, s);
+        case Backend::OddRows: return run_forward_gen(d, Lo, true, xin, lam, rho, out, ws, hist, s);
+        case Backend::OddRowsT: break;  // (returned above)
+    }
+    return fail(ADMM_TV_EINVAL, "run_forward: no backend");
 }
 
 // what a stateful solve refuses (admm_tv_forward_state, admm_tv_state_workspace_size, admm_tv_path(desc, 2))
@@ -2332,9 +2356,14 @@ int run_forward_state(const admm_tv_desc& d, const float* xin, const float* kern
         return 0;
     }
     if (int e = setup(d, Lo, ws, kern, rho, s)) return e;
-    if (Lo.mixed) return fused_forward(MixedOps(d, Lo, ws), xin, lam, rho, out, nullptr, s, &st);
-    if (Lo.gen) return run_forward_gen<float>(d, Lo, xin, lam, rho, out, ws, nullptr, s, &st);
-    return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, nullptr, s, &st);
+    switch (backend_of(d, Lo, 2)) {
+        case Backend::Pow2: return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, nullptr, s, &st);
+        case Backend::Mixed: return fused_forward(MixedOps(d, Lo, ws), xin, lam, rho, out, nullptr, s, &st);
+        case Backend::Generic: return run_forward_gen<float>(d, Lo, false, xin, lam, rho, out, ws, nullptr, s, &st);
+        case Backend::OddRows:
+        case Backend::OddRowsT: break;  // (the odd-length row pass carries no state: never answered for mode 2)
+    }
+    return fail(ADMM_TV_EINVAL, "run_forward_state: no backend");
 }
 
 // backward workspace = forward layout + a^ ping-pong (4 images) + b^ + per-iteration partials
@@ -2361,10 +2390,11 @@ BwdLayout make_bwd_layout(const admm_tv_desc& d) {
     for (int i = 0; i < 4; ++i) B.abar[i] = take(img);
     B.bbar = take(img);  // per module; summed into gxin at the end
     const long long rows = (long long)G * d.B * d.C * d.H;
-    if (B.f.mixed_train) {  // mixed-radix reverse row pass: strips of R rows (a device-independent rule)
+    const Backend be = backend_of(d, B.f, 1);
+    if (be == Backend::Mixed) {  // mixed-radix reverse row pass: strips of R rows (a device-independent rule)
         B.R = strip_rows_mixed((int)d.H, rows, (int)d.W / 2, 512);
         B.nstrips = rows / B.R;
-    } else if (B.f.gen) {  // generic backward: one partial pair per 256-pixel block
+    } else if (be == Backend::Generic) {  // generic backward: one partial pair per 256-pixel block
         B.R = 0;
         B.nstrips = (rows * d.W + 255) / 256;
     } else {
@@ -2383,7 +2413,7 @@ BwdLayout make_bwd_layout(const admm_tv_desc& d) {
         B.xppg = 8;
         B.xgroups = (int)((d.B * d.C + B.xppg - 1) / B.xppg);
         // fused paths: per-plane-group cross-spectrum partials; generic: one 2-D spectrum set
-        const bool generic_x = B.f.gen && !B.f.mixed_train;
+        const bool generic_x = be == Backend::Generic;
         // a PSF bank: plane groups of one table each (T x cpt of them), A_t real fp64 and Z_t complex fp64 per table
         // -- 24 bytes per half-spectrum point and table -- and the separable taps' phase tables and k rows of
         // W/2 + 1 complex fp64 sums per table
@@ -2430,7 +2460,7 @@ int run_backward_gen(const admm_tv_desc& d, const BwdLayout& BL, const T* xin, c
     const int H = (int)d.H, W = (int)d.W, K = d.maxit;
     const long long npx = P * H * W;
     const long long HW = (long long)H * W;
-    const HistView<T> hv(d, hist);
+    const HistView<T> hv(d, Lo, hist);
     const bool psf_grad = gkern != nullptr;
     const int Wh = W / 2 + 1;
     const long long nf = (long long)Wh * H;
@@ -2560,7 +2590,7 @@ int fused_backward(const B& be, const BwdLayout& BL, const float* xin, const flo
     void* ws = be.ws;
     const int H = be.H, N = be.N, W = (int)d.W, K = d.maxit, G = ngroups_of(d);
     const long long Pm = d.B * d.C, P = G * Pm;  // planes of one module, of all modules
-    const HistView<float> hv(d, hist);
+    const HistView<float> hv(d, Lo, hist);
     const bool psf_grad = B::kPsfGrad && gkern != nullptr;
     const long long nf = (long long)(N + 1) * H;
     // a PSF bank (one module): the cross spectra in plane groups of one table each, reduced per table
@@ -2711,11 +2741,16 @@ int run_backward(const admm_tv_desc& d, const float* xin, const float* kern, con
         if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(float) * d.kh * d.kw, s));
         return 0;
     }
-    if (!hist || hist_bytes < make_hist(d).total) return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
+    if (!hist || hist_bytes < make_hist(d, Lo).total) return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
     if (int e = setup(d, Lo, ws, kern, rho, s)) return e;
-    if (Lo.mixed_train) return fused_backward(MixedOps(d, Lo, ws), BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, s);
-    if (Lo.gen) return run_backward_gen(d, BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, ws, s);
-    return fused_backward(Pow2Ops(d, Lo, ws), BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, s);
+    switch (backend_of(d, Lo, 1)) {
+        case Backend::Pow2: return fused_backward(Pow2Ops(d, Lo, ws), BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, s);
+        case Backend::Mixed: return fused_backward(MixedOps(d, Lo, ws), BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, s);
+        case Backend::Generic: return run_backward_gen(d, BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, ws, s);
+        case Backend::OddRows:
+        case Backend::OddRowsT: break;  // (training never runs the odd-length row pass: never answered for mode 1)
+    }
+    return fail(ADMM_TV_EINVAL, "run_backward: no backend");
 }
 
 // ------------------------------------------------------------------ fp64 solves (ADMM_TV_FLAG_F64)
@@ -2739,7 +2774,7 @@ int run_forward_f64(const admm_tv_desc& d, const double* xin, const double* kern
         return 0;
     }
     if (int e = setup<double>(d, Lo, ws, kern, rho, s)) return e;
-    return run_forward_gen<double>(d, Lo, xin, lam, rho, out, ws, hist, s);
+    return run_forward_gen<double>(d, Lo, false, xin, lam, rho, out, ws, hist, s);
 }
 
 int run_backward_f64(const admm_tv_desc& d, const double* xin, const double* kern, const double* lam,
@@ -2764,7 +2799,7 @@ int run_backward_f64(const admm_tv_desc& d, const double* xin, const double* ker
         if (gkern) HIPCHK(hipMemsetAsync(gkern, 0, sizeof(double) * d.kh * d.kw, s));
         return 0;
     }
-    if (!hist || hist_bytes < make_hist(d).total) return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
+    if (!hist || hist_bytes < make_hist(d, BL.f).total) return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
     if (int e = setup<double>(d, BL.f, ws, kern, rho, s)) return e;
     return run_backward_gen<double>(d, BL, xin, lam, rho, gout, hist, gxin, glam, grho, gkern, ws, s);
 }
@@ -2785,21 +2820,18 @@ int admm_tv_supported_f64(int64_t H, int64_t W) { return f64_hw(H, W) ? 1 : 0; }
 int admm_tv_path(const admm_tv_desc* d, int train) {
     if (int e = validate(d)) return e;
     if (int e = bank_check(*d, train == 1)) return e;
-    if (train == 2) {  // admm_tv_forward_state: the fused paths, else the generic loop (also where the plain
-                       // solve takes the odd-length row pass, which carries no state)
+    if (train == 2) {  // admm_tv_forward_state
         if (int e = state_check(*d)) return e;
-        const Layout Lo = make_layout(*d);
-        return !Lo.gen ? ADMM_TV_PATH_FUSED : Lo.mixed ? ADMM_TV_PATH_MIXED : ADMM_TV_PATH_GENERIC;
-    }
-    if (train) {
+    } else if (train) {
         if (int e = grouped_train_check(*d)) return e;
     }
-    if (is_f64(*d)) return ADMM_TV_PATH_GENERIC;  // the generic kernels' double instantiation
-    const Layout Lo = make_layout(*d);
-    if (Lo.tr) return train ? ADMM_TV_PATH_GENERIC : ADMM_TV_PATH_ODD;
-    if (!Lo.gen) return ADMM_TV_PATH_FUSED;
-    if (Lo.mixed && (!train || Lo.mixed_train)) return ADMM_TV_PATH_MIXED;
-    if (Lo.odd && !train) return ADMM_TV_PATH_ODD;
+    switch (backend_of(*d, make_layout(*d), train == 2 ? 2 : train ? 1 : 0)) {
+        case Backend::Pow2: return ADMM_TV_PATH_FUSED;
+        case Backend::Mixed: return ADMM_TV_PATH_MIXED;
+        case Backend::Generic: return ADMM_TV_PATH_GENERIC;
+        case Backend::OddRows:
+        case Backend::OddRowsT: return ADMM_TV_PATH_ODD;
+    }
     return ADMM_TV_PATH_GENERIC;
 }
 
@@ -2855,7 +2887,7 @@ int admm_tv_history_size(const admm_tv_desc* d, size_t* bytes) {
     if (int e = bank_check(*d, true)) return e;
     if (int e = grouped_train_check(*d)) return e;
     if (!bytes) return fail(ADMM_TV_EINVAL, "null bytes");
-    *bytes = make_hist(*d).total;
+    *bytes = make_hist(*d, make_layout(*d)).total;
     return 0;
 }
 
@@ -2868,7 +2900,7 @@ int admm_tv_forward_train(const admm_tv_desc* dp, const float* xin, const float*
     if (is_f64(*dp)) return fail(ADMM_TV_EINVAL, "ADMM_TV_FLAG_F64: use admm_tv_forward_train_f64");
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
-    if (dp->maxit > 0 && (!hist || hist_bytes < make_hist(*dp).total))
+    if (dp->maxit > 0 && (!hist || hist_bytes < make_hist(*dp, make_layout(*dp)).total))
         return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
     if (int e = dg.check()) return e;
@@ -2955,7 +2987,7 @@ int admm_tv_forward_train_f64(const admm_tv_desc* dp, const double* xin, const d
     if (!is_f64(*dp)) return fail(ADMM_TV_EINVAL, "admm_tv_forward_train_f64 needs ADMM_TV_FLAG_F64");
     if (((!xin || !out) && !participate_only(*dp)) || !lam || !rho || (dp->kh > 0 && !kern))
         return fail(ADMM_TV_EINVAL, "null pointer argument");
-    if (dp->maxit > 0 && (!hist || hist_bytes < make_hist(*dp).total))
+    if (dp->maxit > 0 && (!hist || hist_bytes < make_hist(*dp, make_layout(*dp)).total))
         return fail(ADMM_TV_EWORKSPACE, "history buffer too small");
     DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
     if (int e = dg.check()) return e;
