@@ -168,8 +168,9 @@ int admm_tv_supported(int64_t H, int64_t W);
  *   0: admm_tv_forward;
  *   1: admm_tv_forward_train and admm_tv_backward;
  *   2: admm_tv_forward_state: ADMM_TV_PATH_FUSED or ADMM_TV_PATH_MIXED where admm_tv_forward reports
- *      them, ADMM_TV_PATH_GENERIC at every other size, the odd row lengths included.
- * Mode 2 also returns the code with which admm_tv_forward_state refuses the descriptor (its "Refused"
+ *      them, ADMM_TV_PATH_GENERIC at every other size, the odd row lengths included;
+ *   3: admm_tv_forward_box: ADMM_TV_PATH_FUSED at power-of-two sizes, ADMM_TV_PATH_GENERIC at every other.
+ * Modes 2 and 3 also return the code with which their call refuses the descriptor (its "Refused"
  * list), so the query agrees with the call.  Host-only (no device call); tests and benchmarks name the path they measured with it. */
 #define ADMM_TV_PATH_FUSED 1    /* power-of-two two-pass iteration (admm_kernels.hpp) */
 #define ADMM_TV_PATH_GENERIC 2  /* generic kernels: column pass, row inverse, step + row forward */
@@ -229,6 +230,35 @@ int admm_tv_forward_state(const admm_tv_desc* desc, const float* xin, const floa
                           const float* lambda_dev, const float* rho_dev,
                           const admm_tv_state* state_in, const admm_tv_state* state_out,
                           float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------- bounds on x
+ * admm_tv_forward with lo <= x <= hi: min_x 1/2 ||k * x - y||^2 + lambda ||D x||_1  s.t.  lo <= x <= hi
+ * (non-negative intensities: {0, +inf}; an image in [0, 1]: {0, 1}).  The constraint is a third split, w = x,
+ * beside z = Dx, with one scaled dual v and the same rho; everything else is the reference's iteration
+ * (deconv.py:103-115), b = H_t(xin) and the zero start (w_0 = v_0 = 0) included:
+ *     fc_box = 1 / (|sigma|^2 + rho (|dx|^2 + |dy|^2 + 1))
+ *     x_k = irfft2( fc_box rfft2( b + rho (Dx^T (z_x - u_x) + Dy^T (z_y - u_y)) + rho (w - v) ) )
+ *     z, u as in admm_tv_forward
+ *     p = x_k + v;  w = min(max(p, lo), hi);  v = p - w
+ * `out` is x_K, the last x, as everywhere in this ABI: it approaches the bounds as the iteration converges but
+ * is not clamped (clamp it for a feasible image).  With infinite bounds v stays 0 and w = x_k, but rho x_k
+ * remains in the right-hand side: a proximal-point variant with admm_tv_forward's limit, NOT its iterates.
+ *  - bounds_dev: a device float[2] = {lo, hi}, read on the device like lambda and rho; +-infinity allowed.
+ *  - Conventions as admm_tv_forward: asynchronous, allocates nothing, no host synchronisation, runs on the
+ *    stream's device, no per-solve global state.  maxit == 0 writes zeros.  kh == kw == 0 (TV denoising with
+ *    bounds) is valid.
+ *  - The workspace (admm_tv_box_workspace_size) is admm_tv_forward's plus one image for v.
+ *  - Paths (admm_tv_path(desc, 3)): ADMM_TV_PATH_FUSED at power-of-two sizes (the row pass projects the row it
+ *    finalises: one more image read and written per iteration), ADMM_TV_PATH_GENERIC at every other size, the
+ *    smooth sizes and the odd row lengths included.
+ *  - Refused, by admm_tv_box_workspace_size and admm_tv_path(desc, 3) as by the call: ADMM_TV_FLAG_F64,
+ *    ADMM_TV_FLAG_PSF_GRAD, ADMM_TV_FLAG_PSF_BANK_TRAIN (ADMM_TV_EINVAL); a PSF-bank bit, groups > 1, an
+ *    all-reduce hook, more than 2^31 - 1 image rows (B*C*H) at a size the generic kernels serve
+ *    (ADMM_TV_EUNSUPPORTED); by the call, a null bounds_dev (ADMM_TV_EINVAL). */
+int admm_tv_box_workspace_size(const admm_tv_desc* desc, size_t* bytes);
+int admm_tv_forward_box(const admm_tv_desc* desc, const float* xin, const float* kern,
+                        const float* lambda_dev, const float* rho_dev, const float* bounds_dev,
+                        float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* fp64 variants (desc->flags must hold ADMM_TV_FLAG_F64; the plain entry points refuse it): the
  * same contracts as admm_tv_forward / admm_tv_forward_train / admm_tv_backward with double arrays. */

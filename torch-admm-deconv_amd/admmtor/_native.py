@@ -40,6 +40,8 @@ EXPORTED = (
     "admm_tv_forward",
     "admm_tv_state_workspace_size",
     "admm_tv_forward_state",
+    "admm_tv_box_workspace_size",
+    "admm_tv_forward_box",
     "admm_tv_forward_f64",
     "admm_tv_forward_train_f64",
     "admm_tv_backward_f64",
@@ -207,6 +209,10 @@ def _open(path: str) -> ctypes.CDLL:
     stp = ctypes.POINTER(AdmmTvState)
     L.admm_tv_forward_state.restype = ctypes.c_int
     L.admm_tv_forward_state.argtypes = [dp, vp, vp, vp, vp, stp, stp, vp, vp, sz, vp]
+    L.admm_tv_box_workspace_size.restype = ctypes.c_int
+    L.admm_tv_box_workspace_size.argtypes = [dp, ctypes.POINTER(sz)]
+    L.admm_tv_forward_box.restype = ctypes.c_int
+    L.admm_tv_forward_box.argtypes = [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.admm_tv_history_size.restype = ctypes.c_int
     L.admm_tv_history_size.argtypes = [dp, ctypes.POINTER(sz)]
     for f in ("admm_tv_forward_train", "admm_tv_forward_train_f64"):
@@ -294,6 +300,12 @@ def state_workspace_size(d: AdmmTvDesc) -> int:
     return int(n.value)
 
 
+def box_workspace_size(d: AdmmTvDesc) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().admm_tv_box_workspace_size(ctypes.byref(d), ctypes.byref(n)))
+    return int(n.value)
+
+
 def state_of(zx, zy, ux, uy) -> AdmmTvState:
     """admm_tv_state over four tensors (the caller keeps them alive for the call)."""
     return AdmmTvState(zx.data_ptr(), zy.data_ptr(), ux.data_ptr(), uy.data_ptr())
@@ -302,7 +314,7 @@ def state_of(zx, zy, ux, uy) -> AdmmTvState:
 def path(d: AdmmTvDesc, train: bool = False, mode: int = None) -> str:
     """The kernel path a solve of descriptor `d` takes (admm_tv_path): "fused", "generic",
     "fused mixed-radix" or "fused odd-length".  mode (overrides train): 0 admm_tv_forward, 1 the training
-    entry points, 2 admm_tv_forward_state."""
+    entry points, 2 admm_tv_forward_state, 3 admm_tv_forward_box."""
     code = load().admm_tv_path(ctypes.byref(d), int(mode) if mode is not None else (1 if train else 0))
     if code < 0:
         check(code)

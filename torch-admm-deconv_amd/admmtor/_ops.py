@@ -12,6 +12,8 @@ graph, with no graph break, and the autograd formula is registered on the op its
   admm_hip::fft_admm_tv_state(x, lam, rho, kern, state, iso, maxit) -> (out, z_x, z_y, u_x, u_y)
       the stateful inference solve (admm_tv_forward_state): iterations from `state` (the reference's
       z_x, z_y, u_x, u_y, or an empty list for zeros), the state afterwards as new tensors
+  admm_hip::fft_admm_tv_box(x, lam, rho, kern, bounds, iso, maxit) -> out
+      the inference solve with bounds on x (admm_tv_forward_box): bounds is a device (2,) tensor {lo, hi}
   admm_hip::fft_admm_tv_fwd_train(x, lam, rho, kern, iso, maxit, psf_grad) -> (out, hist)
       the training forward (admm_tv_forward_train): hist is the uint8 history the backward reads
   admm_hip::fft_admm_tv_bwd(gout, x, lam, rho, kern, hist, iso, maxit, psf_grad,
@@ -43,7 +45,7 @@ from torch import Tensor
 
 from . import _native
 
-__all__ = ["fft_admm_tv_fwd", "fft_admm_tv_state", "fft_admm_tv_fwd_train", "fft_admm_tv_bwd",
+__all__ = ["fft_admm_tv_fwd", "fft_admm_tv_state", "fft_admm_tv_box", "fft_admm_tv_fwd_train", "fft_admm_tv_bwd",
            "fft_admm_tv_bank_fwd_train", "fft_admm_tv_bank_bwd"]
 
 
@@ -145,6 +147,33 @@ def fft_admm_tv_state(x: Tensor, lam: Tensor, rho: Tensor, kern: Tensor, state: 
 @fft_admm_tv_state.register_fake
 def _(x, lam, rho, kern, state, iso, maxit):
     return tuple(torch.empty_like(x, memory_format=torch.contiguous_format) for _ in range(5))
+
+
+# ---------------------------------------------------------------- inference with bounds on x
+@torch.library.custom_op("admm_hip::fft_admm_tv_box", mutates_args=())
+def fft_admm_tv_box(x: Tensor, lam: Tensor, rho: Tensor, kern: Tensor, bounds: Tensor, iso: bool, maxit: int) -> Tensor:
+    """admm_tv_forward_box: the solve with lo <= x <= hi, bounds = {lo, hi} as a (2,) device tensor read on the
+    device.  Returns x_K, not clamped.  fp32, one module, one PSF."""
+    _check_device(x, lam, rho, kern, bounds)
+    if x.dtype != torch.float32 or lam.numel() != 1:
+        raise NotImplementedError("admm_hip::fft_admm_tv_box: fp32, one module (lam, rho of one element)")
+    if bounds.numel() != 2 or bounds.dtype != torch.float32 or bounds.device != x.device:
+        raise ValueError("admm_hip::fft_admm_tv_box: bounds is an fp32 tensor of two elements {lo, hi} on x's device")
+    B, C, H, W = x.shape
+    _check_supported(H, W, False)
+    d = _desc(x, lam, kern, iso, maxit, _bank(x, kern))  # (a PSF bank: refused by the library)
+    x, lam, rho, kern, bounds = x.contiguous(), lam.contiguous(), rho.contiguous(), kern.contiguous(), bounds.contiguous()
+    ws = torch.empty(_native.box_workspace_size(d), dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(x)
+    _native.check(_native.load().admm_tv_forward_box(
+        d, x.data_ptr(), kern.data_ptr() if _k(kern) > 0 else None, lam.data_ptr(), rho.data_ptr(),
+        bounds.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return out
+
+
+@fft_admm_tv_box.register_fake
+def _(x, lam, rho, kern, bounds, iso, maxit):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 # ---------------------------------------------------------------- training forward + backward

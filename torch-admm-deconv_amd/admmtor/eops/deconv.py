@@ -37,6 +37,7 @@ __all__ = [
     "ADMMState",
     "fft_admm_tv_state",
     "fft_admm_tv_until",
+    "fft_admm_tv_box",
     "fft_admm_tv_bank",
     "fft_admm_tv_bank_state",
     "fft_admm_tv_bank_train",
@@ -303,6 +304,75 @@ def fft_admm_tv_state(xin: torch.Tensor, lmbd, rho, kern: torch.Tensor, iso: boo
         out, zx, zy, ux, uy = torch.ops.admm_hip.fft_admm_tv_state(
             xc, _as_device_scalar(lmbd, dev), _as_device_scalar(rho, dev), kc, sin, bool(iso), maxit)
     return out.to(device=home), ADMMState(zx, zy, ux, uy)
+
+
+def _stage_bounds(lo, hi, dev) -> torch.Tensor:
+    """lo, hi (Python numbers or 0-d / 1-element tensors) -> one fp32 (2,) tensor {lo, hi} on `dev`.  Tensors
+    are never read on the host, so only Python numbers are checked for lo > hi."""
+    if not isinstance(lo, torch.Tensor) and not isinstance(hi, torch.Tensor):
+        if float(lo) > float(hi):
+            raise ValueError(f"fft_admm_tv_box: lo = {lo} is above hi = {hi}")
+        return torch.tensor([float(lo), float(hi)], dtype=torch.float32, device=dev)
+    return torch.cat([_as_device_scalar(lo, dev), _as_device_scalar(hi, dev)])
+
+
+def fft_admm_tv_box(xin: torch.Tensor, lmbd, rho, kern: torch.Tensor, lo=0.0, hi=float("inf"), iso: bool = False,
+                    maxit: int = 100, project: bool = True) -> torch.Tensor:
+    """ADMM-TV deconvolution with bounds on x: ``min_x 1/2 ||k * x - y||^2 + lmbd ||D x||_1`` subject to
+    ``lo <= x <= hi`` -- non-negative intensities (the default, ``(0, inf)``), an image in ``[0, 1]``.
+
+    The constraint is a third split ``w = x`` beside ``z = D x``, with one scaled dual ``v`` and the same
+    ``rho``; everything else is :func:`fft_admm_tv`'s iteration, ``b = H_t(xin)`` and the zero start included::
+
+        fc_box = 1 / (|sigma|^2 + rho (|dx|^2 + |dy|^2 + 1))
+        x_k = irfft2(fc_box rfft2(b + rho (Dx^T (z_x - u_x) + Dy^T (z_y - u_y)) + rho (w - v)))
+        z, u  as in fft_admm_tv
+        p = x_k + v;  w = clamp(p, lo, hi);  v = p - w
+
+    This is the constrained minimiser's iteration, not a clamp after the solve: the ringing the constraint
+    removes is gone from the whole image.  With infinite bounds ``v`` stays 0 and ``w = x_k``, but ``rho x_k``
+    remains in the right-hand side, so the iterates are a proximal-point variant with :func:`fft_admm_tv`'s
+    limit -- they are NOT :func:`fft_admm_tv`'s iterates at a finite ``maxit``.
+
+    ``lo`` and ``hi`` are Python numbers or 0-d / 1-element tensors (staged into one device ``float[2]``, read on
+    the device; tensors are not read on the host); Python numbers with ``lo > hi`` raise ``ValueError``;
+    one-sided bounds use ``-inf`` / ``inf``.  ``project=True`` returns ``x_K.clamp(lo, hi)``, so the result is
+    feasible; ``project=False`` returns the library's ``x_K`` untouched (it approaches the bounds as the
+    iteration converges).
+
+    Inference only, fp32, one module, one PSF: if gradients are enabled and an input requires grad the call
+    raises, as :func:`fft_admm_tv_state` does; fp64 inputs raise ``NotImplementedError`` (there are no fp64
+    kernels for the projection).  Input checks and host staging are :func:`fft_admm_tv`'s: host tensors are
+    staged to the current ROCm device and the result comes back on ``xin``'s device.  Power-of-two sizes run
+    the fused row pass, every other size the generic kernels (``_native.path(desc, mode=3)``).
+    """
+    if not isinstance(kern, torch.Tensor):
+        kern = torch.as_tensor(kern)
+    _check_inputs(xin, kern)
+    if xin.dtype == torch.float64:
+        raise NotImplementedError("fft_admm_tv_box: fp32 solves only (bounds on x in fp64 are not implemented)")
+    if torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad
+                                       for v in (xin, lmbd, rho, kern, lo, hi)):
+        raise RuntimeError("fft_admm_tv_box is inference only: an input requires grad; fft_admm_tv is the "
+                           "differentiable call (or run under torch.no_grad())")
+    home = xin.device
+    maxit = max(0, int(maxit))
+    if not isinstance(lo, torch.Tensor) and not isinstance(hi, torch.Tensor) and float(lo) > float(hi):
+        raise ValueError(f"fft_admm_tv_box: lo = {lo} is above hi = {hi}")
+    if xin.numel() == 0:
+        return torch.zeros(xin.shape, dtype=torch.float32, device=home)
+    xin, lmbd, rho, kern = _stage(xin, lmbd, rho, kern)
+    dev = xin.device
+    with torch.no_grad():
+        xc = xin.detach().to(torch.float32).contiguous()
+        kc = kern.detach().to(device=dev, dtype=torch.float32).contiguous() if kern.numel() > 0 else \
+            torch.empty(0, dtype=torch.float32, device=dev)
+        bounds = _stage_bounds(lo, hi, dev)
+        out = torch.ops.admm_hip.fft_admm_tv_box(xc, _as_device_scalar(lmbd, dev), _as_device_scalar(rho, dev), kc,
+                                                 bounds, bool(iso), maxit)
+        if project:
+            out = torch.clamp(out, bounds[0], bounds[1])
+    return out.to(device=home)
 
 
 def _check_bank(xin: torch.Tensor, kerns: torch.Tensor, who: str) -> None:

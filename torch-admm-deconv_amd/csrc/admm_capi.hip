@@ -212,12 +212,15 @@ struct Layout {
 //   Generic   the generic kernels' three-launch iteration (run_forward_gen / run_backward_gen)
 //   OddRows   the generic column pass and the fused odd-length row pass (aniso inference)
 //   OddRowsT  OddRows on the transposed problem
-// mode: 0 inference, 1 training (forward with a history, backward), 2 stateful inference (fp32: state_check)
+// mode: 0 inference, 1 training (forward with a history, backward), 2 stateful inference (fp32: state_check),
+//       3 inference with bounds on x (fp32: box_check)
 enum class Backend { Pow2, Mixed, Generic, OddRows, OddRowsT };
 Backend backend_of(const admm_tv_desc& d, const Layout& Lo, int mode) {
-    if (mode != 2 && is_f64(d)) return Backend::Generic;  // the generic kernels' double instantiation
-    if (mode != 2 && Lo.tr) return mode == 0 ? Backend::OddRowsT : Backend::Generic;
+    if (mode < 2 && is_f64(d)) return Backend::Generic;  // the generic kernels' double instantiation
+    if (mode < 2 && Lo.tr) return mode == 0 ? Backend::OddRowsT : Backend::Generic;
     if (!Lo.gen) return Backend::Pow2;
+    // (the projection and its dual exist in the power-of-two row pass and the generic step only)
+    if (mode == 3) return Backend::Generic;
     if (Lo.mixed && (mode != 1 || Lo.mixed_train)) return Backend::Mixed;
     // (the odd-length row pass keeps no history and carries no state)
     if (mode == 0 && Lo.odd) return Backend::OddRows;
@@ -411,6 +414,10 @@ template <int N> struct RowOps {
     template <bool ISO, bool FIRST, bool HIST, bool PL> static void pa(const PassAArgs& a, unsigned nb, hipStream_t s) {
         hipLaunchKernelGGL((k_pass_a<N, ISO, FIRST, HIST, PL>), dim3(nb), dim3(G::NT), G::lds_bytes(), s, a);
     }
+    // the solve with bounds on x (k_pass_a BOX): the plain walk, at every row width the kernel is built for
+    template <bool ISO, bool FIRST, bool PL> static void pa_box(const PassAArgs& a, unsigned nb, hipStream_t s) {
+        hipLaunchKernelGGL((k_pass_a<N, ISO, FIRST, false, PL, false, false, true>), dim3(nb), dim3(G::NT), G::lds_bytes(), s, a);
+    }
     // the cooperative variant (admm_kernels.hpp k_pass_a COOP): aniso inference at 1,024-pixel rows
     // (sub-groups of one wave; the iso variant of it spills at 3 waves per SIMD and is not built)
     static constexpr bool kCoop = N == 512;
@@ -429,6 +436,20 @@ template <int N> struct RowOps {
                       bool coop = false, bool pf = false) {
         const unsigned nb = blocks(a.nstrips);
         const int sel = (iso ? 4 : 0) | (first ? 2 : 0) | (hist ? 1 : 0);
+        if (a.v) {  // bounds on x: the plain kernel's BOX instantiation, also where inference runs the cooperative one
+            if (hist) return fail(ADMM_TV_EINVAL, "k_pass_a: bounds on x in a training pass");
+            switch ((iso ? 4 : 0) | (first ? 2 : 0) | (pl ? 1 : 0)) {
+                case 0: pa_box<false, false, false>(a, nb, s); break;
+                case 1: pa_box<false, false, true>(a, nb, s); break;
+                case 2: pa_box<false, true, false>(a, nb, s); break;
+                case 3: pa_box<false, true, true>(a, nb, s); break;
+                case 4: pa_box<true, false, false>(a, nb, s); break;
+                case 5: pa_box<true, false, true>(a, nb, s); break;
+                case 6: pa_box<true, true, false>(a, nb, s); break;
+                default: pa_box<true, true, true>(a, nb, s); break;
+            }
+            return launch_check("k_pass_a<box>");
+        }
         if (kCoop && coop && !iso && !hist && !a.rev && a.R >= 2 && a.nstrips % G::SG == 0 &&
             (a.H / a.R) % G::SG == 0) {
             static_assert(!kCoop || passa_coop_lds<N>() <= 53 * 1024, "three blocks of the row pass per CU");
@@ -789,8 +810,9 @@ int setup_bank(const admm_tv_desc& d, const Layout& Lo, void* ws, const float* k
 }
 
 // setup: twiddle tables, PSF spectrum, Wiener factor (if rho given), centred-PSF multiplier
+// box: the Wiener factor of the solve with bounds on x (k_spectra: + rho in the denominator)
 template <class T>
-int setup(const admm_tv_desc& d, const Layout& Lo, void* ws, const T* kern, const T* rho, hipStream_t s) {
+int setup(const admm_tv_desc& d, const Layout& Lo, void* ws, const T* kern, const T* rho, hipStream_t s, bool box = false) {
     using C = cx_t<T>;
     ProfScope ps(3, s);
     const int H = (int)d.H, W = (int)d.W, N = W / 2, k = d.kh;
@@ -821,7 +843,7 @@ int setup(const admm_tv_desc& d, const Layout& Lo, void* ws, const T* kern, cons
             hipLaunchKernelGGL(k_spectra<T>, dim3((n + nt - 1) / nt), dim3(nt), 0, s, at<double2>(ws, Lo.G),
                                at<double2>(ws, Lo.twHd), rho + g, at<T>(ws, Lo.fcT) + (size_t)g * n, at<C>(ws, Lo.mT),
                                k, H, N, W, Lo.sigma ? at<double2>(ws, Lo.sigma) : nullptr,
-                               (std::is_same<T, double>::value ? 1.0 / ((double)H * W) : spectra_scale(H, W)));
+                               (std::is_same<T, double>::value ? 1.0 / ((double)H * W) : spectra_scale(H, W)), box ? 1 : 0);
             if (int e = launch_check("k_spectra")) return e;
             if constexpr (std::is_same<T, float>::value) if (!Lo.gen) {
                 float* fc = at<float>(ws, Lo.fcT) + (size_t)g * n;
@@ -1370,7 +1392,8 @@ int grow_fwd(const T* img, cx_t<T>* spec, const cx_t<T>* tw, int W, long long ro
     });
 }
 // the step fused into the row transform of r (k_grow_fwd_step; inference iterations)
-template <bool ISO, bool FIRST, class T>
+// (BOX: with bounds on x, fp32 -- g.v and g.bounds set)
+template <bool ISO, bool FIRST, class T, bool BOX = false>
 int grow_fwd_step_t(const GStepArgsT<T>& g, cx_t<T>* spec, const cx_t<T>* tw, int W, long long rows, hipStream_t s,
                     cx_t<T>* gscr, int ldw) {
     const GPlan pl = make_plan(W, kF64<T>);
@@ -1383,13 +1406,13 @@ int grow_fwd_step_t(const GStepArgsT<T>& g, cx_t<T>* spec, const cx_t<T>* tw, in
         const dim3 grid = gen_grid((rows + 2 * a.lines - 1) / (2 * a.lines), pl, kCsz<T>);
         if constexpr (BM == 0 && !kF64<T> && !GLB) {
             if (gen_wide(W, pl)) {
-                if (int e = set_lds(k_grow_fwd_step<BM, TWG, ISO, FIRST, kGenWide>, lds)) return e;
-                hipLaunchKernelGGL((k_grow_fwd_step<BM, TWG, ISO, FIRST, kGenWide>), grid, dim3(kGenWide), lds, s, a, g);
+                if (int e = set_lds(k_grow_fwd_step<BM, TWG, ISO, FIRST, kGenWide, float, false, BOX>, lds)) return e;
+                hipLaunchKernelGGL((k_grow_fwd_step<BM, TWG, ISO, FIRST, kGenWide, float, false, BOX>), grid, dim3(kGenWide), lds, s, a, g);
                 return launch_check("k_grow_fwd_step");
             }
         }
-        if (int e = set_lds(k_grow_fwd_step<BM, TWG, ISO, FIRST, GNT, T, GLB>, lds)) return e;
-        hipLaunchKernelGGL((k_grow_fwd_step<BM, TWG, ISO, FIRST, GNT, T, GLB>), grid,
+        if (int e = set_lds(k_grow_fwd_step<BM, TWG, ISO, FIRST, GNT, T, GLB, BOX>, lds)) return e;
+        hipLaunchKernelGGL((k_grow_fwd_step<BM, TWG, ISO, FIRST, GNT, T, GLB, BOX>), grid,
                            dim3(kF64<T> || GLB ? GNT : gen_threads("ADMM_GROW_NT")), lds, s, a, g);
         return launch_check("k_grow_fwd_step");
     });
@@ -1397,6 +1420,14 @@ int grow_fwd_step_t(const GStepArgsT<T>& g, cx_t<T>* spec, const cx_t<T>* tw, in
 template <class T>
 int grow_fwd_step(const GStepArgsT<T>& g, cx_t<T>* spec, const cx_t<T>* tw, int W, long long rows, bool iso,
                   bool first, hipStream_t s, cx_t<T>* gscr = nullptr, int ldw = 0) {
+    if constexpr (!kF64<T>) {
+        if (g.v) {
+            if (iso) return first ? grow_fwd_step_t<true, true, T, true>(g, spec, tw, W, rows, s, gscr, ldw)
+                                  : grow_fwd_step_t<true, false, T, true>(g, spec, tw, W, rows, s, gscr, ldw);
+            return first ? grow_fwd_step_t<false, true, T, true>(g, spec, tw, W, rows, s, gscr, ldw)
+                         : grow_fwd_step_t<false, false, T, true>(g, spec, tw, W, rows, s, gscr, ldw);
+        }
+    }
     if (iso) return first ? grow_fwd_step_t<true, true>(g, spec, tw, W, rows, s, gscr, ldw)
                           : grow_fwd_step_t<true, false>(g, spec, tw, W, rows, s, gscr, ldw);
     return first ? grow_fwd_step_t<false, true>(g, spec, tw, W, rows, s, gscr, ldw)
@@ -1595,6 +1626,18 @@ template <class T> int gstep(const GStepArgsT<T>& a, bool iso, bool first, bool 
     if (rows > 0x7fffffffLL) return fail(ADMM_TV_EUNSUPPORTED, "too many image rows for the generic step kernel");
     const dim3 grid((unsigned)rows, (unsigned)((a.W + 255) / 256)), blk(256);
     const int sel = (iso ? 4 : 0) | (first ? 2 : 0) | (hist ? 1 : 0);
+    if constexpr (!kF64<T>) {
+        if (a.v) {  // bounds on x (inference: the step outside the row transform, ADMM_GSTEP_FUSE=0)
+            if (hist) return fail(ADMM_TV_EINVAL, "k_gstep: bounds on x in a training step");
+            switch (sel) {
+                case 0: hipLaunchKernelGGL((k_gstep<false, false, false, T, true>), grid, blk, 0, s, a); break;
+                case 2: hipLaunchKernelGGL((k_gstep<false, true, false, T, true>), grid, blk, 0, s, a); break;
+                case 4: hipLaunchKernelGGL((k_gstep<true, false, false, T, true>), grid, blk, 0, s, a); break;
+                default: hipLaunchKernelGGL((k_gstep<true, true, false, T, true>), grid, blk, 0, s, a); break;
+            }
+            return launch_check("k_gstep<box>");
+        }
+    }
     switch (sel) {
         case 0: hipLaunchKernelGGL((k_gstep<false, false, false, T>), grid, blk, 0, s, a); break;
         case 1: hipLaunchKernelGGL((k_gstep<false, false, true, T>), grid, blk, 0, s, a); break;
@@ -1754,11 +1797,18 @@ int state_export(const admm_tv_desc& d, const Layout& Lo, void* ws, const float*
 }
 
 
+// A solve with bounds on x (admm_tv_forward_box): {lo, hi} on the device and the image of the scaled dual v
+// (the workspace's last region).  One module, fp32 inference, no state.
+struct BoxIO {
+    const float* bounds;
+    float* v;
+};
+
 // generic-size forward (same contract as run_forward; generic_kernels.hpp)
 // odd_rows (Backend::OddRows: fp32 aniso inference, no state): the two-launch iteration on the odd-length row pass
 template <class T>
 int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, bool odd_rows, const T* xin, const T* lam, const T* rho,
-                    T* out, void* ws, void* hist, hipStream_t s, const StateIO* sio = nullptr) {
+                    T* out, void* ws, void* hist, hipStream_t s, const StateIO* sio = nullptr, const BoxIO* box = nullptr) {
     using C = cx_t<T>;
     const long long P = d.B * d.C;
     const int H = (int)d.H, W = (int)d.W;
@@ -1883,6 +1933,12 @@ int run_forward_gen(const admm_tv_desc& d, const Layout& Lo, bool odd_rows, cons
         {
             ProfScope ps(0, st);
             GStepArgsT<T> ga{xk, cb, uxi, uyi, uxo, uyo, last ? nullptr : crimg, nsq, nprev, lam, rho, H, W, np * H * W};
+            if constexpr (!kF64<T>) {
+                if (box) {  // bounds on x: this part's planes of v (each pixel reads and writes its own)
+                    ga.v = box->v + io;
+                    ga.bounds = box->bounds;
+                }
+            }
             // inference: the step runs inside the row transform of r (ADMM_GSTEP_FUSE=0: separate)
             if (!train && !last && env_int("ADMM_GSTEP_FUSE", 1)) {
                 if (int e = grow_fwd_step(ga, cspec, twW, W, crows, d.iso != 0, first, st, gs, ld)) return e;
@@ -2024,7 +2080,10 @@ struct Pow2Ops : FusedOps {
         with_row(N, [&](auto ops) { return L = decltype(ops)::G::L; });
         return L;
     }
-    int strip(long long rows, bool aniso_fwd) const { return strip_rows(H, N, rows, aniso_fwd, coop && !rev); }
+    // (plain: the row pass runs the plain kernel whatever the knobs say -- a solve with bounds on x)
+    int strip(long long rows, bool aniso_fwd, bool plain = false) const {
+        return strip_rows(H, N, rows, aniso_fwd, coop && !rev && !plain);
+    }
     int r2c(const float* img, cf* spec, long long rows, hipStream_t s, bool pl = false) const {
         return with_row(N, [&](auto ops) { return decltype(ops)::r2c(img, spec, twW, rows, s, pl); });
     }
@@ -2081,7 +2140,7 @@ struct MixedOps : FusedOps {
     int modules_per_pass(int) const { return 1; }
     bool lane_paired(bool) const { return false; }  // pixel order throughout
     int row_lanes() const { return 0; }
-    int strip(long long rows, bool) const { return strip_rows_mixed(H, rows, N); }
+    int strip(long long rows, bool, bool = false) const { return strip_rows_mixed(H, rows, N); }
     int r2c(const float* img, cf* spec, long long rows, hipStream_t s, bool = false) const {
         return hip_code(admm_mixed::r2c(N, img, spec, twW, rows, s), "k_row_r2c_m");
     }
@@ -2160,7 +2219,7 @@ struct MixedOps : FusedOps {
 // two plane halves on two streams -- DESIGN.md §9; both no faster at C3)
 template <class B>
 int fused_forward(const B& be, const float* xin, const float* lam, const float* rho, float* out, void* hist,
-                  hipStream_t s, const StateIO* sio = nullptr) {
+                  hipStream_t s, const StateIO* sio = nullptr, const BoxIO* box = nullptr) {
     const admm_tv_desc& d = be.d;
     const Layout& Lo = be.Lo;
     void* ws = be.ws;
@@ -2182,7 +2241,7 @@ int fused_forward(const B& be, const float* xin, const float* lam, const float* 
     const int ng = be.modules_per_pass(G);
     const long long np = ng * Pm, rows = np * H;  // planes and rows of a pass
     const int gpm = Lo.ngroups / G;               // iso plane groups per module (a group never straddles two)
-    const int R = be.strip(rows, !d.iso && !train);
+    const int R = be.strip(rows, !d.iso && !train, box != nullptr);
     const bool sin = sio && sio->in, sout = sio && sio->out;
     const int sl = pl ? be.row_lanes() : 0;  // the state kernels' view of the u / b layout
     for (int g0 = 0; g0 < G; g0 += ng) {
@@ -2258,6 +2317,10 @@ int fused_forward(const B& be, const float* xin, const float* lam, const float* 
                 cf* tout = (keep_t && it < d.maxit) ? hv.r(it + 1) : spec[1 - cur];
                 PassAArgs pa{spec[cur], tout, bimg, uxi, uyi, uxo, uyo, nsq, nprev, lamg, rhog, be.twW, H, R, rows / R, Pm,
                              be.rev};
+                if (box) {  // bounds on x (Pow2Ops: the row pass's BOX instantiation)
+                    pa.v = box->v;
+                    pa.bounds = box->bounds;
+                }
                 if (int e = be.pass_a(pa, d.iso != 0, first, train, s, pl)) return e;
             }
             cur = 1 - cur;
@@ -2364,6 +2427,48 @@ int run_forward_state(const admm_tv_desc& d, const float* xin, const float* kern
         case Backend::OddRowsT: break;  // (the odd-length row pass carries no state: never answered for mode 2)
     }
     return fail(ADMM_TV_EINVAL, "run_forward_state: no backend");
+}
+
+// what a solve with bounds on x refuses (admm_tv_forward_box, admm_tv_box_workspace_size, admm_tv_path(desc, 3))
+int box_check(const admm_tv_desc& d) {
+    if (d.flags & (ADMM_TV_FLAG_F64 | ADMM_TV_FLAG_PSF_GRAD | ADMM_TV_FLAG_PSF_BANK_TRAIN))
+        return fail(ADMM_TV_EINVAL, "admm_tv_forward_box: fp32 inference only (ADMM_TV_FLAG_F64 / ADMM_TV_FLAG_PSF_GRAD / "
+                                    "ADMM_TV_FLAG_PSF_BANK_TRAIN set)");
+    if (is_bank(d)) return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_box: no PSF bank (ADMM_TV_FLAG_PSF_PER_IMAGE / _PER_CHANNEL)");
+    if (d.groups > 1) return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_box: groups > 1 (one solve with bounds per module)");
+    if (d.allreduce) return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_box: no cross-rank all-reduce hook");
+    // the generic step kernel runs one block row per image row: B C H < 2^31 at the sizes it serves
+    if (!supported_hw(d.H, d.W) && d.B * d.C * d.H > 0x7fffffffLL)
+        return fail(ADMM_TV_EUNSUPPORTED, "admm_tv_forward_box: more than 2^31 - 1 image rows (B C H) on the generic kernels");
+    return 0;
+}
+
+// the workspace of a solve with bounds on x: the forward's regions, then the image of v
+size_t box_v_offset(const Layout& Lo) { return up(Lo.total); }
+size_t box_total(const admm_tv_desc& d, const Layout& Lo) {
+    return box_v_offset(Lo) + up((size_t)d.B * d.C * d.H * d.W * sizeof(float));
+}
+
+// The solver with bounds on x (admm_tv_forward_box's contract, its descriptor already validated): run_forward's
+// inference iterations with the Wiener factor of the split w = x and the projection in the row pass / the step.
+int run_forward_box(const admm_tv_desc& d, const float* xin, const float* kern, const float* lam, const float* rho,
+                    const float* bounds, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
+    const Layout Lo = make_layout(d);
+    if (int e = check_workspace(ws, ws_bytes, box_total(d, Lo))) return e;
+    if (d.maxit == 0) {  // x = zeros (deconv.py:61,117)
+        HIPCHK(hipMemsetAsync(out, 0, (size_t)d.B * d.C * d.H * d.W * sizeof(float), s));
+        return 0;
+    }
+    if (int e = setup(d, Lo, ws, kern, rho, s, true)) return e;
+    const BoxIO box{bounds, at<float>(ws, box_v_offset(Lo))};  // (v_0 = 0: the first row pass reads no v)
+    switch (backend_of(d, Lo, 3)) {
+        case Backend::Pow2: return fused_forward(Pow2Ops(d, Lo, ws), xin, lam, rho, out, nullptr, s, nullptr, &box);
+        case Backend::Generic: return run_forward_gen<float>(d, Lo, false, xin, lam, rho, out, ws, nullptr, s, nullptr, &box);
+        case Backend::Mixed:
+        case Backend::OddRows:
+        case Backend::OddRowsT: break;  // (never answered for mode 3)
+    }
+    return fail(ADMM_TV_EINVAL, "run_forward_box: no backend");
 }
 
 // backward workspace = forward layout + a^ ping-pong (4 images) + b^ + per-iteration partials
@@ -2819,13 +2924,16 @@ int admm_tv_supported_f64(int64_t H, int64_t W) { return f64_hw(H, W) ? 1 : 0; }
 
 int admm_tv_path(const admm_tv_desc* d, int train) {
     if (int e = validate(d)) return e;
+    if (train == 3) {  // admm_tv_forward_box (its refusals come ahead of a bank's own)
+        if (int e = box_check(*d)) return e;
+    }
     if (int e = bank_check(*d, train == 1)) return e;
     if (train == 2) {  // admm_tv_forward_state
         if (int e = state_check(*d)) return e;
-    } else if (train) {
+    } else if (train && train != 3) {
         if (int e = grouped_train_check(*d)) return e;
     }
-    switch (backend_of(*d, make_layout(*d), train == 2 ? 2 : train ? 1 : 0)) {
+    switch (backend_of(*d, make_layout(*d), train == 2 || train == 3 ? train : train ? 1 : 0)) {
         case Backend::Pow2: return ADMM_TV_PATH_FUSED;
         case Backend::Mixed: return ADMM_TV_PATH_MIXED;
         case Backend::Generic: return ADMM_TV_PATH_GENERIC;
@@ -2880,6 +2988,25 @@ int admm_tv_forward_state(const admm_tv_desc* dp, const float* xin, const float*
     if (int e = dg.check()) return e;
     return run_forward_state(*dp, xin, kern, lam, rho, StateIO{state_in, state_out}, out, ws, ws_bytes,
                              reinterpret_cast<hipStream_t>(stream));
+}
+
+int admm_tv_box_workspace_size(const admm_tv_desc* d, size_t* bytes) {
+    if (int e = validate(d)) return e;
+    if (int e = box_check(*d)) return e;
+    if (!bytes) return fail(ADMM_TV_EINVAL, "null bytes");
+    *bytes = box_total(*d, make_layout(*d));  // the forward's regions, then v
+    return 0;
+}
+
+int admm_tv_forward_box(const admm_tv_desc* dp, const float* xin, const float* kern, const float* lam, const float* rho,
+                        const float* bounds, float* out, void* ws, size_t ws_bytes, void* stream) {
+    if (int e = validate(dp)) return e;
+    if (int e = box_check(*dp)) return e;
+    if (!bounds) return fail(ADMM_TV_EINVAL, "admm_tv_forward_box: null bounds_dev (a device float[2] = {lo, hi})");
+    if (!xin || !out || !lam || !rho || (dp->kh > 0 && !kern)) return fail(ADMM_TV_EINVAL, "null pointer argument");
+    DeviceGuard dg(reinterpret_cast<hipStream_t>(stream));
+    if (int e = dg.check()) return e;
+    return run_forward_box(*dp, xin, kern, lam, rho, bounds, out, ws, ws_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 int admm_tv_history_size(const admm_tv_desc* d, size_t* bytes) {
@@ -2961,7 +3088,7 @@ int admm_tv_psf_transpose(const admm_tv_desc* dp, const float* xin, const float*
     }
     hipLaunchKernelGGL(k_spectra<float>, dim3((n + 255) / 256), dim3(256), 0, s, at<double2>(ws, Lo.G),
                        at<double2>(ws, Lo.twHd), at<float>(ws, Lo.fcT), at<float>(ws, Lo.spec[1]),
-                       at<cf>(ws, Lo.mT), d.kh, H, N, W, nullptr, spectra_scale(H, W));
+                       at<cf>(ws, Lo.mT), d.kh, H, N, W, nullptr, spectra_scale(H, W), 0);
     if (int e = launch_check("k_spectra")) return e;
     if (Lo.gen) return gapply(xin, out, at<cf>(ws, Lo.spec[0]), Lo, ws, d, 1, s);
     return psf_transpose_into(d, Lo, ws, xin, out, at<cf>(ws, Lo.spec[0]), 1, s);

@@ -190,13 +190,14 @@ static __global__ void k_psf_rows_bank(const float* __restrict__ kern, double2* 
 }
 
 // fcT[kx][ky] = scale / (|sigma|^2 + rho (|Dx^|^2 + |Dy^|^2));
+// (box: + rho in the denominator, the x-update of the solve with bounds -- the split w = x adds rho I)
 // mT[kx][ky] = scale * sigma * exp(+2 pi i c (ky/H + kx/W))  (centred PSF, c = k/2)
 // scale = 1/(2HW) for the packed power-of-two path, 1/(HW) for the generic path
 template <class T>
 __device__ __forceinline__ void spectra_body(const double2* __restrict__ G, const double2* __restrict__ twHd,
                                              const T* __restrict__ rho_p, T* __restrict__ fcT,
                                              cx_t<T>* __restrict__ mT, int k, int H, int N, int W,
-                                             double2* __restrict__ sigma_out, double scale) {
+                                             double2* __restrict__ sigma_out, double scale, int box = 0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (N + 1) * H) return;
     const int kx = i / H, ky = i % H;
@@ -214,7 +215,7 @@ __device__ __forceinline__ void spectra_body(const double2* __restrict__ G, cons
     const double rho = (double)rho_p[0];
     const double sx = sinpi((double)kx / W), sy = sinpi((double)ky / H);
     const double lap = 4.0 * sx * sx + 4.0 * sy * sy;
-    fcT[i] = (T)(scale / (sr * sr + si * si + rho * lap));
+    fcT[i] = (T)(scale / (sr * sr + si * si + rho * (box ? lap + 1.0 : lap)));
     if (k > 0) {
         const int c = k / 2;  // ceil((k-1)/2): anchor of the reference's H_t
         const long long ph = (long long)c * ky * W + (long long)c * kx * H;  // units of 1/(H W)
@@ -227,8 +228,8 @@ __device__ __forceinline__ void spectra_body(const double2* __restrict__ G, cons
 template <class T = float>
 __global__ void k_spectra(const double2* __restrict__ G, const double2* __restrict__ twHd,
                           const T* __restrict__ rho_p, T* __restrict__ fcT, cx_t<T>* __restrict__ mT, int k,
-                          int H, int N, int W, double2* __restrict__ sigma_out, double scale) {
-    spectra_body<T>(G, twHd, rho_p, fcT, mT, k, H, N, W, sigma_out, scale);
+                          int H, int N, int W, double2* __restrict__ sigma_out, double scale, int box) {
+    spectra_body<T>(G, twHd, rho_p, fcT, mT, k, H, N, W, sigma_out, scale, box);
 }
 // a bank: table blockIdx.y of G, fcT and mT (one rho for the bank)
 static __global__ void k_spectra_bank(const double2* __restrict__ G, const double2* __restrict__ twHd,
@@ -699,6 +700,19 @@ __global__ void __launch_bounds__(CP * (H / RowCfg<H>::E), PASSB2_MINW)
 
 
 // ---------------------------------------------------------------------------
+// bounds on x (admm_tv_forward_box): the split w = x with the scaled dual v.  At a pixel with x = x_k and
+// v = v_{k-1}: p = x + v, w = clamp(p, lo, hi), v_k = p - w, and the x-update's right-hand side gains
+// rho (w - v_k) = rho (2 w - p).  One expression for the fused row pass and the generic step, so that the
+// two paths agree to rounding.  Returns r + rho (2 w - p) and leaves v_k in vn.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float box_term(float x, float v, float lo, float hi, float rho, float r, float& vn) {
+    const float p = x + v;
+    const float w = fminf(fmaxf(p, lo), hi);
+    vn = p - w;
+    return fmaf(rho, (w + w) - p, r);
+}
+
+// ---------------------------------------------------------------------------
 // pass A: the fused row pass of one ADMM iteration, one sub-group per strip of R rows
 //
 // State between iterations (per plane, two images):
@@ -727,6 +741,10 @@ struct PassAArgs {
                           // module m = plane / ppm has lam[m], rho[m], norms at nsq + m 2HW, and
                           // all modules share b (b has ppm planes)
     int rev = 0;          // 1: walk the strips from the last one (ADMM_PASSA_REV, A/B)
+    // BOX (admm_tv_forward_box): the scaled dual v of the split w = x, in the layout of u, updated in place
+    // (a strip reads and writes only the rows it finalises, never its halo rows), and {lo, hi}
+    float* v = nullptr;   // [P][H][W]
+    const float* bounds = nullptr;
 };
 
 // occupancy target of the row pass (waves per SIMD): 3 for rows up to W = 1024 (fits
@@ -735,6 +753,13 @@ struct PassAArgs {
 #define PASSA_MINW_SMALL 3
 #endif
 #define PASSA_MINW(n) ((n) >= 1024 ? 1 : PASSA_MINW_SMALL)
+// ... of its BOX instantiations: the finalised row's x stays in registers until its r is formed (the plain
+// kernel drops it after a_y), E more complex values per lane where the plain kernel already uses 152-164 of the
+// 168 VGPRs three waves leave.  At 3 waves per SIMD rows of 128 to 1,024 pixels spilled 12-164 B per lane, so
+// those run at 2 (up to 256 VGPRs, no scratch); the narrow rows fit as they are.
+#ifndef PASSA_MINW_BOX
+#define PASSA_MINW_BOX(n) ((n) >= 1024 ? 1 : (n) >= 64 ? 2 : PASSA_MINW_SMALL)
+#endif
 
 template <bool ISO, class T> __device__ __forceinline__ T shrink_z(T a, T tau, T nsum) {
     if constexpr (ISO) return block_factor(nsum, tau) * a;
@@ -787,9 +812,14 @@ template <int N> constexpr size_t passa_coop_lds() {
 // that of ydir / finish / xdir below: sharing it through helpers changed the code the compiler makes for
 // the 90 other instantiations of this kernel, which stay as they are.  Same operands in the same order:
 // bit-identical (tests/test_gpu_passa_pipeline.py compares the two forms).
-template <int N, bool ISO, bool FIRST, bool HIST, bool PL, bool COOP = false, bool PF = false>
-__global__ void __launch_bounds__(256, PF ? 2 : PASSA_MINW(N)) k_pass_a(PassAArgs a) {
+//
+// BOX (the solve with bounds on x, plain walk only): when a row is finalised its x is in hand (xprev), so
+// the projection and its dual live here -- box_term above on the row's v, loaded and stored like the
+// loop's u images (FIRST: zeros; no store in a solve's last row pass, as for u).
+template <int N, bool ISO, bool FIRST, bool HIST, bool PL, bool COOP = false, bool PF = false, bool BOX = false>
+__global__ void __launch_bounds__(256, PF ? 2 : BOX ? PASSA_MINW_BOX(N) : PASSA_MINW(N)) k_pass_a(PassAArgs a) {
     static_assert(!(PL && HIST), "the training history keeps the pixel-order layout");
+    static_assert(!BOX || (!COOP && !HIST), "bounds on x: the plain walk of an inference solve");
     using G = RowKernelGeom<N>;
     constexpr int E = G::E, L = G::L, W = G::W, SG = G::SG;
     static_assert(!COOP || (L == 64 && SG % 2 == 0 && !HIST && !ISO), "cooperative strips: whole waves in pairs, aniso inference");
@@ -838,6 +868,9 @@ __global__ void __launch_bounds__(256, PF ? 2 : PASSA_MINW(N)) k_pass_a(PassAArg
     const cf* nsy = reinterpret_cast<const cf*>(a.nsq + moff + (size_t)H * W);
     const cf* npx = reinterpret_cast<const cf*>(a.nsq_prev + moff);
     const cf* npy = reinterpret_cast<const cf*>(a.nsq_prev + moff + (size_t)H * W);
+    // BOX: the plane's v and the bounds (kernel arguments: read once per block, on scalar registers)
+    cf* vimg = BOX ? reinterpret_cast<cf*>(a.v + poff) : nullptr;
+    const float blo = BOX ? a.bounds[0] : 0.f, bhi = BOX ? a.bounds[1] : 0.f;
 
     // The parts of a row step.  A strip walked downwards runs them for rows i0 .. i0 + R with the row
     // above in hand; walked upwards (COOP) it runs the same parts with the row below in hand.
@@ -888,7 +921,8 @@ __global__ void __launch_bounds__(256, PF ? 2 : PASSA_MINW(N)) k_pass_a(PassAArg
         }
     };
     // ---- finalize row gm: v = Dx^T w_x + Dy^T w_y (wyp, wyc: w_y of rows gm, gm + 1), r = b + rho v, row FFT
-    auto finish = [&](int gm, const cf (&wxp)[E], const cf (&wyp)[E], const cf (&wyc)[E]) __attribute__((always_inline)) {
+    // (BOX: xm is row gm's x; r gains rho (2 w - p) and v of the row is updated in place)
+    auto finish = [&](int gm, const cf (&wxp)[E], const cf (&wyp)[E], const cf (&wyc)[E], const cf (&xm)[E]) __attribute__((always_inline)) {
         {
             const size_t rm = (size_t)gm * N;
             cf r[E], sh[E], bv[E];
@@ -902,6 +936,24 @@ __global__ void __launch_bounds__(256, PF ? 2 : PASSA_MINW(N)) k_pass_a(PassAArg
                 const float v0 = (wxp[j].x - wxp[j].y) + (wyp[j].x - wyc[j].x);
                 const float v1 = (wxp[j].y - wr) + (wyp[j].y - wyc[j].y);
                 r[j] = mkc(fmaf(rho, v0, bb.x), fmaf(rho, v1, bb.y));
+            }
+            if constexpr (BOX) {
+                cf vv[E];
+                if constexpr (FIRST) {
+#pragma unroll
+                    for (int j = 0; j < E; ++j) vv[j] = mkc(0.f, 0.f);
+                } else {
+                    ld_row<E, L, PL, (ADMM_NT & 16) != 0>(vimg + rm, t, vv);
+                }
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    float n0, n1;
+                    const float r0 = box_term(xm[j].x, vv[j].x, blo, bhi, rho, r[j].x, n0);
+                    const float r1 = box_term(xm[j].y, vv[j].y, blo, bhi, rho, r[j].y, n1);
+                    r[j] = mkc(r0, r1);
+                    vv[j] = mkc(n0, n1);
+                }
+                if (ust) st_row<E, L, PL, (ADMM_NT & 1) != 0>(vimg + rm, t, vv);
             }
             RowXf<N>::r2c(r, buf, tw, t);
 #pragma unroll
@@ -978,7 +1030,7 @@ __global__ void __launch_bounds__(256, PF ? 2 : PASSA_MINW(N)) k_pass_a(PassAArg
             wa[j] = pick(up, wyc[j], wyp[j]);
             wb[j] = pick(up, wyp[j], wyc[j]);
         }
-        finish(gf, wxp, wa, wb);
+        finish(gf, wxp, wa, wb, xprev);  // (BOX, the downward walk: xprev is row gf's x)
     };
     auto shift = [&]() __attribute__((always_inline)) {
 #pragma unroll

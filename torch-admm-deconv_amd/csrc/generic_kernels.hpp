@@ -714,6 +714,9 @@ template <class T> struct GStepArgsT {
     const T* rho;
     int H, W;
     long long npx;       // P H W
+    // BOX (admm_tv_forward_box, fp32): the scaled dual v of the split w = x, updated in place, and {lo, hi}
+    T* v = nullptr;
+    const T* bounds = nullptr;
 };
 using GStepArgs = GStepArgsT<float>;
 
@@ -732,7 +735,8 @@ __device__ __forceinline__ T gprev_u(const T* __restrict__ src, const T* __restr
 // (b + rho D^T w; unused when a.r is null in k_gstep)
 // (the image pointers as __restrict__ parameters: after inlining the compiler may move one
 // pixel's loads above another's stores, so a thread's pixels overlap their memory latency)
-template <bool ISO, bool FIRST, bool HIST, class T>
+// (BOX: r gains rho (2 w - p) and the pixel's v is updated, admm_kernels.hpp box_term)
+template <bool ISO, bool FIRST, bool HIST, class T, bool BOX = false>
 __device__ __forceinline__ T gstep_pxr(const GStepArgsT<T>& a, const T* __restrict__ xs, const T* __restrict__ bs,
                                        const T* __restrict__ uxs, const T* __restrict__ uys, T* __restrict__ uxd,
                                        T* __restrict__ uyd, unsigned row, int j) {
@@ -776,27 +780,35 @@ __device__ __forceinline__ T gstep_pxr(const GStepArgsT<T>& a, const T* __restri
     uxd[P0] = HIST ? ax : nux;
     uyd[P0] = HIST ? ay : nuy;
     const T v = (wx - wxR) + (wy - wyD);
-    return fmat(rho, v, bs[P0]);
+    if constexpr (BOX) {
+        static_assert(std::is_same<T, float>::value && !HIST, "bounds on x: fp32 inference");
+        float vn;
+        const float r = box_term(x, FIRST ? 0.f : a.v[P0], a.bounds[0], a.bounds[1], rho, fmat(rho, v, bs[P0]), vn);
+        a.v[P0] = vn;
+        return r;
+    } else {
+        return fmat(rho, v, bs[P0]);
+    }
 }
 
-template <bool ISO, bool FIRST, bool HIST, class T>
+template <bool ISO, bool FIRST, bool HIST, class T, bool BOX = false>
 __device__ __forceinline__ T gstep_px(const GStepArgsT<T>& a, unsigned row, int j) {
-    return gstep_pxr<ISO, FIRST, HIST>(a, a.x, a.b, a.uxi, a.uyi, a.uxo, a.uyo, row, j);
+    return gstep_pxr<ISO, FIRST, HIST, T, BOX>(a, a.x, a.b, a.uxi, a.uyi, a.uxo, a.uyo, row, j);
 }
 
-template <bool ISO, bool FIRST, bool HIST, class T = float>
+template <bool ISO, bool FIRST, bool HIST, class T = float, bool BOX = false>
 __global__ void __launch_bounds__(256) k_gstep(GStepArgsT<T> a) {
     // grid (rows P H, column chunks): one 32-bit division per thread instead of 64-bit ones
     const int j = (int)(blockIdx.y * blockDim.x + threadIdx.x);
     if (j >= a.W) return;
-    const T r = gstep_px<ISO, FIRST, HIST>(a, blockIdx.x, j);
+    const T r = gstep_px<ISO, FIRST, HIST, T, BOX>(a, blockIdx.x, j);
     if (a.r) a.r[(size_t)blockIdx.x * a.W + j] = r;
 }
 
 // the step fused into the next row transform (inference): a block computes r_{k+1} for its
 // 2 lines rows pixel by pixel (gstep_px, writing u_k) straight into the LDS image of k_grow_fwd,
 // so r never goes through HBM (-8 B/px and one launch per iteration)
-template <int BM, bool ISO, bool FIRST, class T>
+template <int BM, bool ISO, bool FIRST, class T, bool BOX = false>
 __device__ __forceinline__ void grow_fwd_step_item(const GRowArgsT<T>& a, const GStepArgsT<T>& g, cx_t<T>* A,
                                                    cx_t<T>* B, cx_t<T>* X, const cx_t<T>* tw, long long r0) {
     using C = cx_t<T>;
@@ -808,10 +820,10 @@ __device__ __forceinline__ void grow_fwd_step_item(const GRowArgsT<T>& a, const 
             const int rr = 2 * c;
             T v0 = 0, v1 = 0;
             if (rr + 1 < nl) {
-                v0 = gstep_pxr<ISO, FIRST, false>(g, g.x, g.b, g.uxi, g.uyi, g.uxo, g.uyo, (unsigned)(r0 + rr), i);
-                v1 = gstep_pxr<ISO, FIRST, false>(g, g.x, g.b, g.uxi, g.uyi, g.uxo, g.uyo, (unsigned)(r0 + rr + 1), i);
+                v0 = gstep_pxr<ISO, FIRST, false, T, BOX>(g, g.x, g.b, g.uxi, g.uyi, g.uxo, g.uyo, (unsigned)(r0 + rr), i);
+                v1 = gstep_pxr<ISO, FIRST, false, T, BOX>(g, g.x, g.b, g.uxi, g.uyi, g.uxo, g.uyo, (unsigned)(r0 + rr + 1), i);
             } else if (rr < nl) {
-                v0 = gstep_pxr<ISO, FIRST, false>(g, g.x, g.b, g.uxi, g.uyi, g.uxo, g.uyo, (unsigned)(r0 + rr), i);
+                v0 = gstep_pxr<ISO, FIRST, false, T, BOX>(g, g.x, g.b, g.uxi, g.uyi, g.uxo, g.uyo, (unsigned)(r0 + rr), i);
             }
             A[i * lines + c] = mkx<T>(v0, v1);  // even row -> real part, odd row -> imaginary part
         }
@@ -829,7 +841,7 @@ __device__ __forceinline__ void grow_fwd_step_item(const GRowArgsT<T>& a, const 
         }
 }
 
-template <int BM, bool TWG, bool ISO, bool FIRST, int NT = GNT, class T = float, bool GLB = false>
+template <int BM, bool TWG, bool ISO, bool FIRST, int NT = GNT, class T = float, bool GLB = false, bool BOX = false>
 __global__ void __launch_bounds__(NT) k_grow_fwd_step(GRowArgsT<T> a, GStepArgsT<T> g) {
     using C = cx_t<T>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -841,7 +853,7 @@ __global__ void __launch_bounds__(NT) k_grow_fwd_step(GRowArgsT<T> a, GStepArgsT
     if constexpr (!TWG)
         for (int i = threadIdx.x; i < W + a.plan.ntab; i += blockDim.x) twl[i] = a.tw[i];
     const C* tw = TWG ? a.tw : twl;
-#define ADMM_ITEM(r0) grow_fwd_step_item<BM, ISO, FIRST>(a, g, A, B, X, tw, r0)
+#define ADMM_ITEM(r0) grow_fwd_step_item<BM, ISO, FIRST, T, BOX>(a, g, A, B, X, tw, r0)
     ADMM_GEN_ITEMS((a.rows + 2 * lines - 1) / (2 * lines), 2 * lines, ADMM_ITEM)
 #undef ADMM_ITEM
 }
